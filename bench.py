@@ -8,13 +8,20 @@ tachikoma trace binary of the shard (headers, params, records).  One op-trace =
 the complete per-op trace of one sample; value = samples traced by all ranks ÷
 max-over-ranks wall time.  Inputs are resident in HBM before timing starts.
 
-Launch: python bench.py [--gpus N --steps K --warmup W]
+Launch: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+  * a plain run sets up, warms up, times the K steps, writes --dump-outputs if asked and prints the
+    headline line (metric, value, unit, ms_per_step, ...); everything described below the timed
+    region (copy trace, compute-only and block timing, roofline, record digests, file-sink check,
+    PCIe probe, parity against the CPU oracle, CPU baseline) runs only with --full.
+  * --dump-outputs DIR writes the records of the last timed step as DIR/<k>_<name>.npy (a seeded
+    sample of each large record, at most 64 MB in all); the inputs are seeded, so two builds run
+    with the same arguments can be compared output for output.
   * N > 1 without torch.distributed.run: this process starts N rank processes (before any
     GPU call) and exits with their status; with torch.distributed.run (WORLD_SIZE set),
     WORLD_SIZE must equal --gpus.
   * --dist-backend gloo rehearses N ranks on one GPU (all ranks share cuda:0).
 
-After the timed region, the trace image is checked record for record against the CPU
+With --full, after the timed region, the trace image is checked record for record against the CPU
 oracle: at N > 1 every rank checks ceil(64 / N) samples spread over its shard, and rank 0 then
 times the CPU baseline at every N, checking each sample it traces and then (untimed) the rest of
 its shard -- at N = 1 all 64 samples; any mismatch makes the run exit non-zero.
@@ -67,6 +74,14 @@ def parse(argv=None):
     p.add_argument("--warmup", type=int, default=2)
     p.add_argument("--model", default="resnet50")
     p.add_argument("--batch", type=int, default=64, help="samples per GPU (shard size)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run every secondary measurement and check: copy trace, "
+                        "compute-only and block timing, roofline, record digests, file-sink check, PCIe probe, "
+                        "parity against the CPU oracle and the CPU baseline (a plain run prints the headline only)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps write what the last timed step produced (its trace records; the "
+                        "graph output with --no-trace) as DIR/<k>_<name>.npy, float32 (int8 records) or float64 "
+                        "(wider ones): a fixed seeded sample of each record, at most 64 MB in all")
     p.add_argument("--cpu-budget-s", type=float, default=15.0, help="CPU baseline time budget")
     p.add_argument("--skip-cpu", action="store_true")
     p.add_argument("--sink", choices=["memory", "file"], default="memory",
@@ -321,6 +336,37 @@ def find_tune_table(model: str, batch: int):
     return None if best is None else best[1]
 
 
+# ---------------------------------------------------------------- --dump-outputs
+
+DUMP_BUDGET_BYTES = 56 << 20  # sample bytes of one dump: under the 64 MB limit with the .npy headers
+DUMP_SEED = 20240607          # the sample positions depend on this, the array's position and its size only
+
+
+def dump_outputs(out_dir: str, arrays: dict, prefix: str = "") -> list:
+    """Write every array of `arrays` ({name: ndarray}, in order) as <out_dir>/<prefix><k>_<name>.npy:
+    float32 where that holds the dtype exactly (8/16-bit integers, float16/32), float64 otherwise
+    (int32 accumulators).  The arrays share DUMP_BUDGET_BYTES equally; one that fits its share is
+    written whole in its own shape, a larger one as a 1-D sample of its flattened elements at
+    seeded positions (sorted, the same from run to run).  Returns what was written."""
+    import re
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(len(arrays), 1)
+    exact32 = {np.dtype(t) for t in (np.bool_, np.int8, np.uint8, np.int16, np.uint16, np.float16, np.float32)}
+    written = []
+    for k, (name, a) in enumerate(arrays.items()):
+        a = np.asarray(a)
+        out_t = np.float32 if a.dtype in exact32 else np.float64
+        cap = share // np.dtype(out_t).itemsize
+        sampled = a.size > cap
+        if sampled:
+            at = np.sort(np.random.default_rng([DUMP_SEED, k]).integers(0, a.size, size=cap))
+            a = a.reshape(-1)[at]
+        fname = f"{prefix}{k:03d}_{re.sub(r'[^A-Za-z0-9_.-]+', '_', name).strip('_') or 'record'}.npy"
+        np.save(os.path.join(out_dir, fname), a.astype(out_t))
+        written.append({"file": fname, "name": name, "elements": int(a.size), "sampled": bool(sampled)})
+    return written
+
+
 # ---------------------------------------------------------------- one rank
 
 def dump_maps_at_exit() -> None:
@@ -378,8 +424,38 @@ def mount_of(path: str):
     return None if best is None else {"mount": best[0], "type": best[1], "device": best[2]}
 
 
+def headline(args, world: int, elapsed_max: float, pg: bool) -> dict:
+    """The head of the result line, from the timed steps alone (max-over-ranks wall time of
+    --steps traced steps): printed by every run; --full adds its measurements after it."""
+    B = args.batch
+    return {
+        "metric": metric_for(args.model),
+        "value": round(B * world * args.steps / elapsed_max, 3),
+        "unit": "op-traces/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed_max / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "int8",
+        "data": f"synthetic (seeded int8 inputs, random-init int8 weights of the "
+                f"{WORKLOADS.get(args.model, ('', args.model))[1]} topology)",
+        "config": {"workload": f"{args.model} int8 224x224, {B} samples per GPU "
+                               f"({WORKLOADS.get(args.model, ('custom',))[0]}), "
+                               f"full per-op trace to pinned host memory",
+                   "model": args.model, "global_batch": B * world, "samples_per_gpu": B, "seq_len": None,
+                   "parallelism": f"batch-shard x{world}", "sink": args.sink,
+                   "dist_backend": args.dist_backend if pg else None},
+        "full": bool(args.full),
+    }
+
+
 def main(argv=None) -> int:
     args = parse(argv)
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
     check_gpu_count(args)
     if os.environ.get("WORLD_SIZE") is None and args.gpus > 1:
         return launch_ranks(args.gpus, [sys.executable, os.path.abspath(__file__)] +
@@ -609,6 +685,33 @@ def main(argv=None) -> int:
     if writer is not None:
         writer.shutdown()
 
+    # ---- --dump-outputs: what the last timed step left for its caller (the records in its trace
+    # image; the graph output of a compute-only step), before any later step overwrites an image
+    dumped = None
+    if args.dump_outputs:
+        if args.no_trace:
+            outs = {f"output{k}": m.get_output(k).numpy() for k in range(m.get_num_outputs())}
+        else:
+            outs = read_trace(caps[(args.steps - 1) % len(caps)].bytes()).records
+        dumped = dump_outputs(args.dump_outputs, outs, prefix=f"rank{rank}_" if world > 1 else "")
+        _log(f"dumped {len(dumped)} arrays ({sum(d['elements'] for d in dumped)} elements) to {args.dump_outputs}")
+        del outs
+
+    if not args.full:
+        # a plain run ends here: the headline of the timed steps and nothing else
+        if rank == 0:
+            line = headline(args, world, elapsed_max, pg)
+            line["extra"] = {"run_mode": "hip graph per step (tk_module_run_graph)" if m.module.use_graph else
+                             "host-issued kernels and copies (tk_module_run)",
+                             "run_mode_pick": mode_pick, "kernels": tune_info,
+                             "trace_bytes_per_step": caps[0].layout.total, "library": _lib.build_info(),
+                             "dumped_arrays": None if dumped is None else len(dumped)}
+            print(json.dumps(line), flush=True)
+        if pg:
+            dist.destroy_process_group()
+        teardown()
+        return 0
+
     # ---- copy trace of the real traced step (packed graph mode): per chunk, bytes and the copy's
     # start / end on the capture stream after the step's first launch; gaps between chunk copies
     # are time the PCIe link idles inside a step
@@ -830,25 +933,7 @@ def main(argv=None) -> int:
             _log("FILE SINK FAILURE: a written trace file's digest differs from its device digest")
             rc = 1
         line = {
-            "metric": metric_for(args.model),
-            "value": round(value, 3),
-            "unit": "op-traces/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed_max / args.steps * 1e3, 3),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "int8",
-            "data": f"synthetic (seeded int8 inputs, random-init int8 weights of the "
-                    f"{WORKLOADS.get(args.model, ('', args.model))[1]} topology)",
-            "config": {"workload": f"{args.model} int8 224x224, {B} samples per GPU "
-                                   f"({WORKLOADS.get(args.model, ('custom',))[0]}), "
-                                   f"full per-op trace to pinned host memory",
-                       "model": args.model, "global_batch": B * world, "samples_per_gpu": B, "seq_len": None,
-                       "parallelism": f"batch-shard x{world}", "sink": args.sink,
-                       "dist_backend": args.dist_backend if pg else None},
+            **headline(args, world, elapsed_max, pg),
             "roofline": {"bound": "hbm", "achieved": round(achieved_bw / 1e9, 1), "peak": HBM_PEAK_GBPS,
                          "unit": "GB/s", "frac": round(achieved_bw / 1e9 / HBM_PEAK_GBPS, 4),
                          "traffic": None if pmc is None else int(pmc["per_launch"]),

@@ -132,6 +132,44 @@ def test_pmc_traffic_picks_library_then_stamp(tmp_path, monkeypatch):
     assert bench.pmc_traffic("resnet18", 64, "current") is None
 
 
+def test_dump_outputs_is_seeded_exact_and_bounded(tmp_path, monkeypatch):
+    """--dump-outputs: small arrays whole in their own shape, large ones as the same seeded sample
+    from run to run; int8 as float32, int32 as float64 (exact past 2^24); the budget bounds a dump."""
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 3 * 4096)
+    rng = np.random.default_rng(0)
+    big32 = rng.integers(-2**31, 2**31, size=(4, 50, 50), dtype=np.int64).astype(np.int32)
+    arrays = {"data": rng.integers(-128, 128, size=(4, 3, 40, 40)).astype(np.int8), "%0": big32,
+              "%1": np.arange(10, dtype=np.int8).reshape(2, 5)}
+    got = [bench.dump_outputs(str(tmp_path / d), arrays) for d in ("a", "b")]
+    assert got[0] == got[1] and [w["file"] for w in got[0]] == ["000_data.npy", "001_0.npy", "002_1.npy"]
+    assert [w["sampled"] for w in got[0]] == [True, True, False]
+    a = {w["file"]: np.load(tmp_path / "a" / w["file"]) for w in got[0]}
+    b = {w["file"]: np.load(tmp_path / "b" / w["file"]) for w in got[0]}
+    assert all(np.array_equal(a[k], b[k]) and a[k].dtype == b[k].dtype for k in a)
+    assert a["000_data.npy"].dtype == np.float32 and a["001_0.npy"].dtype == np.float64
+    assert a["000_data.npy"].shape == (1024,) and a["001_0.npy"].shape == (512,)
+    assert np.array_equal(a["002_1.npy"], arrays["%1"]) and a["002_1.npy"].shape == (2, 5)
+    flat = big32.reshape(-1).astype(np.float64)
+    assert np.isin(a["001_0.npy"], flat).all() and np.abs(a["001_0.npy"]).max() > 2**24
+    assert sum(v.nbytes for v in a.values()) <= 3 * 4096
+    # other data at the same positions shows in the dump
+    arrays["%0"] = big32 + 1
+    bench.dump_outputs(str(tmp_path / "c"), arrays)
+    assert np.array_equal(np.load(tmp_path / "c" / "001_0.npy"), a["001_0.npy"] + 1)
+
+
+def test_headline_and_plain_run_options():
+    args = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert args.full is False and args.dump_outputs is None
+    assert bench.parse(["--full", "--dump-outputs", "d"]).full is True
+    line = bench.headline(args, 1, 0.7, False)
+    assert line["ms_per_step"] == 100.0 and line["value"] == 640.0 and line["steps"] == 7 and line["warmup"] == 3
+    assert line["metric"] == bench.METRIC and line["unit"] == "op-traces/s" and line["dtype"] == "int8"
+    assert line["higher_is_better"] is True and line["full"] is False
+    with pytest.raises(SystemExit, match="--steps must be at least 1"):
+        bench.main(["--steps", "0"])
+
+
 def test_file_sink_overlap_pick():
     """The r05r box: on / off rounds 860 / 985, 817 / 608, 555 / 606 ms per step -- a median over
     all rounds picked "off" (frac 0.77 where overlap reached 0.90); without the first round the

@@ -1,5 +1,5 @@
 """The RCCL branch of bench.py on the one GPU a box has: a child process starts a
-world-size-1 ``nccl`` process group before any GPU call (bench.py --force-pg), runs every
+world-size-1 ``nccl`` process group before any GPU call (bench.py --full --force-pg), runs every
 collective the N>1 path uses -- barrier, the elapsed-time all_reduce(MAX), the device record-digest
 all_gather over RCCL, all_gather_object of the rank info, the status broadcast -- and writes its
 shard file and manifest; the manifest's digest must equal both the digest of the written file and
@@ -23,7 +23,7 @@ def test_bench_world1_nccl_collectives(tmp_path):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-pg", "--dist-backend", "nccl",
+    cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--force-pg", "--dist-backend", "nccl",
            "--model", "lenet5", "--batch", "8", "--steps", "2", "--warmup", "1", "--skip-cpu", "--tune-table", "none",
            "--sink", "file", "--file-overlap", "off", "--out-dir", str(tmp_path)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)

@@ -41,13 +41,13 @@ for r in "$@"; do
   case "$r" in
     suite) run 900 suite.log python3 -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread ;;
     smoke) run 300 smoke.log python3 -u -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run 400 bench.json python3 -u bench.py --gpus 1 --steps 20 --warmup 5 $BARGS ;;
-    findstep) run 400 bench_find.json python3 -u bench.py --gpus 1 --steps 5 --warmup 2 --skip-cpu \
+    bench) run 400 bench.json python3 -u bench.py --full --gpus 1 --steps 20 --warmup 5 $BARGS ;;
+    findstep) run 400 bench_find.json python3 -u bench.py --full --gpus 1 --steps 5 --warmup 2 --skip-cpu \
         --tune-table none --write-tune-table "$O/tune_table.json" --tune-report "$O/find_step.json" $BARGS ;;
-    host) run 400 bench_host.json python3 -u bench.py --gpus 1 --steps 20 --warmup 5 --skip-cpu --run-mode host ;;
+    host) run 400 bench_host.json python3 -u bench.py --full --gpus 1 --steps 20 --warmup 5 --skip-cpu --run-mode host ;;
     copytrace)
       run 400 copytrace.log bash tools/rocprof_one_hsa.sh --memory-copy-trace --kernel-trace --stats \
-        --output-format csv -d "$O/copy" -o run -- python3 -u bench.py --steps 3 --warmup 1 --skip-cpu \
+        --output-format csv -d "$O/copy" -o run -- python3 -u bench.py --full --steps 3 --warmup 1 --skip-cpu \
         --copy-trace "$O/copy_trace.json" &&
       python3 tools/bench_copy_trace.py "$O/copy" "$O/copy_trace.json" "$O/bench_copy_trace.json" > /dev/null ;;
     copytracetorch)  # control: torch alone under plain rocprofv3 (two HSA runtimes in the process)
@@ -57,29 +57,29 @@ for r in "$@"; do
         -d "$O/copy_probe" -o run -- ./tools/probe_copies tools/resnet50_b64_record_sizes.txt 1 ;;
     copyprobe) run 300 copyprobe.jsonl ./tools/probe_copies tools/resnet50_b64_record_sizes.txt 3 ;;
     prof) run 400 prof.log rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o run -- \
-        python3 -u bench.py --skip-cpu $BARGS ;;
+        python3 -u bench.py --full --skip-cpu $BARGS ;;
     pmc) run 900 pmc.log bash tools/pmc.sh "$O/pmc" "$O/pmc/summary.json" $BARGS ;;
     layers) run 400 layers.log rocprofv3 --kernel-trace --output-format csv -d "$O/layers" -o run -- \
-        python3 -u bench.py --steps 3 --warmup 1 --skip-cpu --no-trace $BARGS ;;
+        python3 -u bench.py --full --steps 3 --warmup 1 --skip-cpu --no-trace $BARGS ;;
     filesink)
       (df -hT /tmp . ; cat /proc/mounts) > "$O/mounts.txt" 2>&1
-      run 600 bench_file.json python3 -u bench.py --gpus 1 --steps 10 --warmup 3 --skip-cpu --sink file --out-dir /tmp
-      run 600 bench_file_overlap.json python3 -u bench.py --gpus 1 --steps 10 --warmup 3 --skip-cpu --sink file \
+      run 600 bench_file.json python3 -u bench.py --full --gpus 1 --steps 10 --warmup 3 --skip-cpu --sink file --out-dir /tmp
+      run 600 bench_file_overlap.json python3 -u bench.py --full --gpus 1 --steps 10 --warmup 3 --skip-cpu --sink file \
         --out-dir /tmp --file-overlap on
-      run 600 bench_file_serial.json python3 -u bench.py --gpus 1 --steps 10 --warmup 3 --skip-cpu --sink file \
+      run 600 bench_file_serial.json python3 -u bench.py --full --gpus 1 --steps 10 --warmup 3 --skip-cpu --sink file \
         --out-dir /tmp --file-overlap off ;;
     filesweep)
       # writer shapes with the overlapped sink: threads, piece size, buffered
       for v in "TK_WRITE_THREADS=1" "TK_WRITE_THREADS=2" "TK_WRITE_THREADS=8" "TK_WRITE_PIECE_MB=256" \
                "TK_WRITE_THREADS=2 TK_WRITE_PIECE_MB=256" "TK_WRITE_BUFFERED=1"; do
         tag=$(echo "$v" | tr ' =' '__')
-        run 300 "bench_file_$tag.json" env $v python3 -u bench.py --gpus 1 --steps 8 --warmup 2 --skip-cpu \
+        run 300 "bench_file_$tag.json" env $v python3 -u bench.py --full --gpus 1 --steps 8 --warmup 2 --skip-cpu \
           --sink file --out-dir /tmp
       done ;;
     realized) run 600 realized.log python3 -u tools/realized_times.py ;;
     splitlayers) run 400 splitlayers.log rocprofv3 --kernel-trace --output-format csv -d "$O/splitlayers" -o run -- \
-        python3 -u bench.py --steps 3 --warmup 1 --skip-cpu --no-trace --tune-table profiles/r04_split_probe_table.json ;;
-    gloo2) run 600 bench_2rank_gloo.json python3 -u bench.py --gpus 2 --dist-backend gloo --steps 10 --warmup 3 ;;
+        python3 -u bench.py --full --steps 3 --warmup 1 --skip-cpu --no-trace --tune-table profiles/r04_split_probe_table.json ;;
+    gloo2) run 600 bench_2rank_gloo.json python3 -u bench.py --full --gpus 2 --dist-backend gloo --steps 10 --warmup 3 ;;
     hostmem)
       # host DRAM bandwidth of the GPU's NUMA node, alone and while a traced bench writes its image
       node=$(python3 -c 'import sys; sys.path.insert(0, "."); from tachikoma_amd import shard; print(shard.pci_numa_node(shard.gpu_pci_address(0)))')

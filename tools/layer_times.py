@@ -1,4 +1,4 @@
-"""Per-layer kernel durations from a rocprofv3 kernel-trace CSV of `bench.py --no-trace`
+"""Per-layer kernel durations from a rocprofv3 kernel-trace CSV of `bench.py --full --no-trace`
 (maps the k-th launch of each kernel family per step onto the plan's exec groups)."""
 import csv
 import re

@@ -7,7 +7,7 @@ is doubled; WRITE_SIZE is exact for 16-B-per-lane streaming stores.  The last
 with the same node list).
 
 usage: python tools/pmc_summary.py <pmc outdir> [launches] [--runs R] [--json out.json]
-(`bench.py --steps 2 --warmup 1 --no-trace` runs 1 + 3*2 + 1 = 8 steps)
+(`bench.py --full --steps 2 --warmup 1 --no-trace` runs 1 + 3*2 + 1 = 8 steps)
 """
 import argparse
 import csv

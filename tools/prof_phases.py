@@ -1,4 +1,4 @@
-"""Split a rocprofv3 kernel trace of ``bench.py`` into its traced and compute-only steps.
+"""Split a rocprofv3 kernel trace of ``bench.py --full`` into its traced and compute-only steps.
 
 rocprofv3 --stats averages every dispatch of a kernel over the whole command.  The
 bench runs traced steps (D2H capture concurrent with the kernels) and compute-only
