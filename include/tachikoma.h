@@ -661,6 +661,52 @@ int tk_module_set_trace_chunks(tk_module* mod, int chunks);
  * the chunk count (out may hold fewer: max_chunks). */
 int tk_module_set_copy_trace(tk_module* mod, int enable);
 int tk_module_copy_trace(tk_module* mod, double* out, int max_chunks);
+/* Trace wire (packed capture only; host-issued runs and graph copy modes 1..5 stay raw): with
+ * wire on (the default; TK_TRACE_WIRE=0 in the environment at tk_module_create forces it off),
+ * int32 records do not cross the link as they are.  After each chunk's graph an encode kernel on
+ * a module-owned wire stream reads them from their own device buffers and writes the wire format
+ * below straight into a pinned host slot (a ring of three worst-case-sized chunk slots); the
+ * other records still go through the mirror, copied in runs of adjacent records on the wire
+ * stream.  A host function on a module-owned decode stream, gated on the event after the chunk's
+ * wire work, widens the slot into the trace image on the decoder's thread pool.  The capture
+ * stream waits for the run's last decode before capture_done is recorded, so synchronising the
+ * capture stream, tk_module_wait_capture and a device synchronise all still mean "the image is
+ * complete", and the image is byte for byte what wire off produces.  A slot is reused once the
+ * decode of its previous use is done; the next run's kernels wait for this run's encodes.
+ * tk_module_wire_stats: after waiting for the last run's decodes, out[3c .. 3c+2] = {wire bytes,
+ * raw bytes of the coded records, decode ms} of chunk c; returns the chunk count (0 when the last
+ * traced run was not a wire run).  tk_module_copy_trace keeps reporting the image bytes a chunk
+ * delivers, over the interval of its wire work on the wire stream. */
+int tk_module_set_trace_wire(tk_module* mod, int enable);
+int tk_module_wire_stats(tk_module* mod, double* out, int max_chunks);
+
+/* Wire format of int32 trace records (csrc/tk_wire.h has the byte layout): blocks of 256 elements
+ * coded as an int32 base (the block minimum) plus offsets of 0..4 bytes each, in byte planes;
+ * a record with diff != 0 is coded as its wrap-around difference from the record before it, which
+ * must have the same element count.  `offset` is the record's byte offset in the trace image
+ * (any alignment).  tk_wire_bound: the worst-case wire size.  tk_wire_encode_host: the reference
+ * encoder (reads the records from `image`), returns the wire bytes written.  tk_wire_decode:
+ * widens `wire` into `image` on up to `threads` pool threads (<= 0: the pool, which is sized from
+ * the CPU affinity mask, at most 16, TK_WIRE_THREADS overrides; tk_wire_threads reports it); a
+ * table or segment that does not lie inside wire_bytes is refused with TK_ERR_INVALID_ARG and
+ * nothing outside `wire` is read.  tk_wire_encode_device: the device encoder on device buffers
+ * src[i] (one per record), writing into `wire` (device-accessible, tk_wire_bound bytes, 64-byte
+ * aligned); synchronises `stream`. */
+typedef struct {
+  int64_t offset;
+  int64_t n_elems;
+  int32_t diff;
+  int32_t reserved;
+} tk_wire_record;
+int64_t tk_wire_bound(const tk_wire_record* recs, int n_recs);
+int64_t tk_wire_encode_host(const tk_wire_record* recs, int n_recs, const void* image, int64_t image_bytes,
+                            void* wire, int64_t wire_cap);
+int tk_wire_decode(const tk_wire_record* recs, int n_recs, const void* wire, int64_t wire_bytes, void* image,
+                   int64_t image_bytes, int threads);
+int tk_wire_encode_device(const tk_wire_record* recs, int n_recs, const void* const* src, void* wire,
+                          int64_t wire_cap, void* stream);
+int tk_wire_threads(void);
+
 /* Makes `stream` wait for the copies of the last traced run: call before writing any
  * tensor the module reads (GraphModule.set_input / load_params,
  * graph_executor.cc:158-166 SetInput) on a stream of your own. */

@@ -307,6 +307,15 @@ class tk_node(ctypes.Structure):
     ]
 
 
+class tk_wire_record(ctypes.Structure):
+    _fields_ = [
+        ("offset", ctypes.c_int64),
+        ("n_elems", ctypes.c_int64),
+        ("diff", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
 class tk_array_meta(ctypes.Structure):
     _fields_ = [
         ("name", ctypes.c_char_p),
@@ -408,6 +417,14 @@ SIGNATURES = {
     "tk_module_set_trace_chunks": (ctypes.c_int, [_VP, ctypes.c_int]),
     "tk_module_set_copy_trace": (ctypes.c_int, [_VP, ctypes.c_int]),
     "tk_module_copy_trace": (ctypes.c_int, [_VP, ctypes.POINTER(_F64), ctypes.c_int]),
+    "tk_module_set_trace_wire": (ctypes.c_int, [_VP, ctypes.c_int]),
+    "tk_module_wire_stats": (ctypes.c_int, [_VP, ctypes.POINTER(_F64), ctypes.c_int]),
+    "tk_wire_bound": (_I64, [ctypes.POINTER(tk_wire_record), ctypes.c_int]),
+    "tk_wire_encode_host": (_I64, [ctypes.POINTER(tk_wire_record), ctypes.c_int, _VP, _I64, _VP, _I64]),
+    "tk_wire_decode": (ctypes.c_int, [ctypes.POINTER(tk_wire_record), ctypes.c_int, _VP, _I64, _VP, _I64, ctypes.c_int]),
+    "tk_wire_encode_device": (ctypes.c_int, [ctypes.POINTER(tk_wire_record), ctypes.c_int, ctypes.POINTER(_VP), _VP,
+                                             _I64, _VP]),
+    "tk_wire_threads": (ctypes.c_int, []),
     "tk_module_tune": (ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32),
                                       ctypes.POINTER(_F32)]),
     "tk_module_set_node_algo": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int]),

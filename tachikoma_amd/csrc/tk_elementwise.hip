@@ -8,6 +8,7 @@
 #include <climits>
 
 #include "tk_common.h"
+#include "tk_wire.h"
 
 namespace tk {
 
@@ -690,6 +691,145 @@ int pack_records_impl(const void* table, int nrec, int64_t blocks, void* mirror,
   TK_CHECK_ARG(table && mirror && nrec > 0 && blocks > 0, "bad arguments");
   hipLaunchKernelGGL(pack_records_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const PackRec*)table, nrec,
                      (uint8_t*)mirror);
+  TK_LAUNCH_CHECK();
+  return TK_OK;
+}
+
+// ---------------------------------------------------------------- trace wire encoder
+// The device side of the wire format (tk_wire.h): one workgroup codes one segment of up to 64
+// blocks of 256 int32 elements, read from the record's own device buffer (minus the predecessor
+// record's element for a differenced record).  16 lanes own a block, 16 consecutive elements
+// each, so a block's minimum and maximum are a 16-lane butterfly and a lane's share of a byte
+// plane is exactly one 16-byte store; the workgroup's 16 lane groups take four passes over the
+// segment, keeping the 64 offsets of a thread in registers.  After the widths are known one
+// thread takes the segment's place from the buffer's cursor (units of 64 B) and publishes it in
+// the table at the front of the buffer; nothing is stored if the place would end past `cap_units`
+// (it cannot: the buffer is sized for every block raw), and the decoder then refuses the entry.
+// The buffer is usually a pinned host slot: every store to it is a full 16-byte plane piece, a
+// header word, or (last, short block of a record only) a byte.
+__global__ __launch_bounds__(256) void wire_encode_kernel(const WireSegDev* __restrict__ segs, uint32_t* cursor,
+                                                          uint32_t* __restrict__ table, uint8_t* __restrict__ payload,
+                                                          uint32_t cap_units) {
+  __shared__ int32_t s_base[kWireSegBlocks];
+  __shared__ uint32_t s_w[kWireSegBlocks];
+  __shared__ uint32_t s_off[kWireSegBlocks];
+  __shared__ uint32_t s_start;
+  const WireSegDev sg = segs[blockIdx.x];
+  const int n = sg.n;
+  const int nb = (n + kWireBlock - 1) / kWireBlock;
+  const int g = threadIdx.x >> 4, l = threadIdx.x & 15;
+  const bool aligned = ((((uintptr_t)sg.src) | ((uintptr_t)sg.prev)) & 15) == 0;
+  uint32_t v[4][16];
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    const int b = p * 16 + g;
+    const int e0 = b * kWireBlock + l * 16;
+    int32_t mn = INT_MAX, mx = INT_MIN;
+    if (aligned && e0 + 16 <= n) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const tk_v4i a = *reinterpret_cast<const tk_v4i*>(sg.src + e0 + 4 * q);
+        v[p][4 * q] = (uint32_t)a.x, v[p][4 * q + 1] = (uint32_t)a.y, v[p][4 * q + 2] = (uint32_t)a.z,
+                 v[p][4 * q + 3] = (uint32_t)a.w;
+      }
+      if (sg.prev) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const tk_v4i a = *reinterpret_cast<const tk_v4i*>(sg.prev + e0 + 4 * q);
+          v[p][4 * q] -= (uint32_t)a.x, v[p][4 * q + 1] -= (uint32_t)a.y, v[p][4 * q + 2] -= (uint32_t)a.z,
+              v[p][4 * q + 3] -= (uint32_t)a.w;
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 16; ++j) mn = min(mn, (int32_t)v[p][j]), mx = max(mx, (int32_t)v[p][j]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        uint32_t x = 0;
+        if (e0 + j < n) {
+          x = (uint32_t)sg.src[e0 + j];
+          if (sg.prev) x -= (uint32_t)sg.prev[e0 + j];
+          mn = min(mn, (int32_t)x), mx = max(mx, (int32_t)x);
+        }
+        v[p][j] = x;
+      }
+    }
+#pragma unroll
+    for (int m = 8; m >= 1; m >>= 1) {
+      mn = min(mn, __shfl_xor(mn, m, 16));
+      mx = max(mx, __shfl_xor(mx, m, 16));
+    }
+    // exact in unsigned arithmetic (mx >= mn as signed values): INT_MIN and INT_MAX in one block
+    // give 2^32 - 1 and the raw width, not a wrapped range
+    const uint32_t range = (uint32_t)mx - (uint32_t)mn;
+    const uint32_t w = range == 0 ? 0 : range <= 0xFFu ? 1 : range <= 0xFFFFu ? 2 : range <= 0xFFFFFFu ? 3 : 4;
+    if (l == 0 && b < nb) s_base[b] = mn, s_w[b] = w;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) v[p][j] -= (uint32_t)mn;
+  }
+  __syncthreads();
+  const uint32_t base_bytes = (uint32_t)((4 * nb + 15) & ~15);
+  const uint32_t hdr = base_bytes + (uint32_t)((nb + 15) & ~15);
+  if (threadIdx.x == 0) {
+    uint32_t off = hdr;
+    for (int b = 0; b < nb; ++b) {
+      s_off[b] = off;
+      off += s_w[b] * (uint32_t)min(kWireBlock, n - b * kWireBlock);
+    }
+    const uint32_t units = (off + 63) >> 6;
+    const uint32_t start = atomicAdd(cursor, units);
+    table[blockIdx.x] = start;
+    s_start = start <= cap_units && units <= cap_units - start ? start : 0xFFFFFFFFu;
+  }
+  __syncthreads();
+  if (s_start == 0xFFFFFFFFu) return;
+  uint8_t* out = payload + (uint64_t)s_start * 64;
+  // header: bases as words, widths four to a word (the padding of both parts written as zeros)
+  if ((int)threadIdx.x < (int)(base_bytes >> 2))
+    reinterpret_cast<int32_t*>(out)[threadIdx.x] = (int)threadIdx.x < nb ? s_base[threadIdx.x] : 0;
+  if ((int)threadIdx.x < (int)((hdr - base_bytes) >> 2)) {
+    uint32_t ww = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int b = (int)threadIdx.x * 4 + j;
+      if (b < nb) ww |= s_w[b] << (8 * j);
+    }
+    reinterpret_cast<uint32_t*>(out + base_bytes)[threadIdx.x] = ww;
+  }
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    const int b = p * 16 + g;
+    if (b >= nb) continue;
+    const int cnt = min(kWireBlock, n - b * kWireBlock);
+    const uint32_t w = s_w[b];
+    uint8_t* q = out + s_off[b];
+    for (uint32_t k = 0; k < w; ++k) {
+      const uint32_t sh = 8 * k;
+      uint32_t o[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        o[c] = ((v[p][4 * c] >> sh) & 0xFFu) | (((v[p][4 * c + 1] >> sh) & 0xFFu) << 8) |
+               (((v[p][4 * c + 2] >> sh) & 0xFFu) << 16) | (((v[p][4 * c + 3] >> sh) & 0xFFu) << 24);
+      if (cnt == kWireBlock) {
+        __builtin_nontemporal_store(tk_v4i{(int)o[0], (int)o[1], (int)o[2], (int)o[3]},
+                                    reinterpret_cast<tk_v4i*>(q + k * kWireBlock + l * 16));
+      } else {
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+          if (l * 16 + j < cnt) q[k * cnt + l * 16 + j] = (uint8_t)(o[j >> 2] >> (8 * (j & 3)));
+      }
+    }
+  }
+}
+
+int wire_encode_impl(const WireSegDev* segs, int64_t n_seg, uint32_t* cursor, void* wire, int64_t wire_bytes,
+                     hipStream_t s) {
+  const int64_t table = wire_table_bytes(n_seg);
+  TK_CHECK_ARG(segs && cursor && wire && n_seg > 0 && n_seg < ((int64_t)1 << 31) && ((uintptr_t)wire & 63) == 0 &&
+               wire_bytes >= table, "bad arguments");
+  const int64_t cap_units = std::min<int64_t>((wire_bytes - table) / 64, 0xFFFFFFF0ll);
+  hipLaunchKernelGGL(wire_encode_kernel, dim3((unsigned)n_seg), dim3(256), 0, s, segs, cursor, (uint32_t*)wire,
+                     (uint8_t*)wire + table, (uint32_t)cap_units);
   TK_LAUNCH_CHECK();
   return TK_OK;
 }

@@ -8,6 +8,8 @@
 // host memory on a second stream, each copy gated by an event recorded right
 // after the node, so the PCIe transfer of node i overlaps the kernels of nodes > i.
 #include <algorithm>
+#include <atomic>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <memory>
@@ -15,6 +17,7 @@
 #include <vector>
 
 #include "tk_common.h"
+#include "tk_wire.h"
 
 namespace tk {
 int requantize_impl(const tk_tensor* x, tk_tensor* y, const tk_requantize_attrs* a, hipStream_t s);
@@ -36,6 +39,8 @@ int postops_impl(const tk_tensor* acc, const tk_tensor* sum_src, tk_tensor* y, c
 int digest_impl(const void* data, int64_t nbytes, uint64_t* out, hipStream_t s);
 int host_copy_impl(const void* const* src, void* const* dst, const int64_t* bytes, int n, hipStream_t s);
 int pack_records_impl(const void* table, int nrec, int64_t blocks, void* mirror, hipStream_t s);
+int wire_encode_impl(const WireSegDev* segs, int64_t n_seg, uint32_t* cursor, void* wire, int64_t wire_bytes,
+                     hipStream_t s);
 int ewise_impl(const tk_tensor* x, const tk_tensor* r, tk_tensor* y, const tk_ewise_attrs* a, hipStream_t s);
 int conv2d_f32_impl(const tk_tensor* x, const tk_tensor* w, tk_tensor* y, const tk_conv2d_attrs* a, hipStream_t s);
 int dense_f32_impl(const tk_tensor* x, const tk_tensor* w, tk_tensor* y, hipStream_t s);
@@ -268,7 +273,40 @@ struct PackPlan {
   std::vector<hipGraph_t> g[2];   // per mirror: one graph per chunk (+ a tail graph)
   std::vector<hipGraphExec_t> ge[2];
   int next = 0;
+  // Trace wire (tk_module_set_trace_wire): the int32 records of a chunk are not packed; an encode
+  // kernel writes them into a pinned slot and a host function widens the slot into the image.
+  bool wire = false;
+  struct Range {
+    int64_t off, len;
+  };
+  struct WireCall {  // what one decode host function works on
+    tk::WireJob job;
+    std::atomic<int>* failed = nullptr;
+  };
+  struct WireChunk {
+    std::vector<Range> raw;  // mirror ranges of the records that are not coded (runs of adjacent ones)
+    int64_t seg_off = 0;     // first entry in `wire_segs`
+    int64_t coded_bytes = 0, bound = 0;
+    std::vector<tk::WireSegHost> segs;
+    std::vector<tk::WireUnit> units;
+    std::unique_ptr<WireCall[]> calls;  // one per slot
+    hipEvent_t landed = nullptr;        // the chunk's wire work is done
+    int last_slot = -1;
+  };
+  std::vector<WireChunk> wchunks;
+  void* wire_segs = nullptr;   // device WireSegDev entries of every chunk
+  std::vector<void*> slots;    // pinned ring of worst-case-sized chunk slots
+  uint32_t* cursors = nullptr; // device, one per slot
+  std::vector<hipEvent_t> slot_done;  // decode of the slot's last use (decode stream)
+  std::vector<char> slot_used;
+  int slot_next = 0;
   ~PackPlan() {
+    for (auto& w : wchunks)
+      if (w.landed) (void)hipEventDestroy(w.landed);
+    for (auto e : slot_done) (void)hipEventDestroy(e);
+    for (void* p : slots) (void)hipHostFree(p);
+    if (wire_segs) (void)hipFree(wire_segs);
+    if (cursors) (void)hipFree(cursors);
     for (int m = 0; m < 2; ++m) {
       for (auto x : ge[m]) (void)hipGraphExecDestroy(x);
       for (auto x : g[m]) (void)hipGraphDestroy(x);
@@ -323,7 +361,16 @@ struct tk_module {
   hipEvent_t ct_t0 = nullptr;
   std::vector<hipEvent_t> ct_ev;
   std::vector<int64_t> ct_bytes;
+  // trace wire of the packed capture: on unless TK_TRACE_WIRE=0 was set when the module was
+  // created; wire traffic and decodes run on two streams of the module's own
+  bool trace_wire = true, wire_forced_off = false;
+  hipStream_t wire_s = nullptr, dec_s = nullptr;
+  hipEvent_t wire_tail = nullptr, decode_tail = nullptr;  // last wire work / decode of the last wire run
+  bool wire_tail_used = false;
+  std::atomic<int> wire_failed{0};
+  PackPlan* last_wire_plan = nullptr;
   void drop_graph() {
+    last_wire_plan = nullptr;
     for (Graph& x : graphs) {
       if (x.ge) (void)hipGraphExecDestroy(x.ge);
       if (x.g) (void)hipGraphDestroy(x.g);
@@ -341,6 +388,10 @@ struct tk_module {
     if (graph_pre) (void)hipEventDestroy(graph_pre);
     if (ct_t0) (void)hipEventDestroy(ct_t0);
     for (auto e : ct_ev) (void)hipEventDestroy(e);
+    if (wire_tail) (void)hipEventDestroy(wire_tail);
+    if (decode_tail) (void)hipEventDestroy(decode_tail);
+    if (wire_s) (void)hipStreamDestroy(wire_s);
+    if (dec_s) (void)hipStreamDestroy(dec_s);
     if (cap_s) (void)hipStreamDestroy(cap_s);
     if (cap_cs) (void)hipStreamDestroy(cap_cs);
     for (hipStream_t x : cap_cx)
@@ -480,6 +531,7 @@ int tk_module_create(const tk_node* nodes, int n_nodes, tk_module** out) {
     return TK_ERR_INVALID_ARG;
   }
   auto mod = std::make_unique<tk_module>();
+  if (const char* e = std::getenv("TK_TRACE_WIRE")) mod->wire_forced_off = e[0] == '0' && e[1] == 0;
   mod->nodes.resize(n_nodes);
   for (int i = 0; i < n_nodes; ++i) {
     const tk_node& src = nodes[i];
@@ -677,6 +729,8 @@ static int build_pack_plan(tk_module* mod, const std::vector<void*>& dst, PackPl
     const void* src;
     int64_t bytes;
     int node;
+    const tk_tensor* t;
+    bool wire, diff;  // coded on the wire; as the difference from the record before it
   };
   std::vector<Rec> recs;
   for (size_t i = 0; i < mod->nodes.size(); ++i) {
@@ -684,9 +738,10 @@ static int build_pack_plan(tk_module* mod, const std::vector<void*>& dst, PackPl
     for (int k = 0; k < n.desc.n_outputs; ++k) {
       char* h = (char*)dst[i * TK_MAX_NODE_OUTPUTS + k];
       const int64_t nb = tk::nbytes(&n.out[k].t);
-      if (h && nb > 0) recs.push_back({h, tk::ptr(&n.out[k].t), nb, (int)i});
+      if (h && nb > 0) recs.push_back({h, tk::ptr(&n.out[k].t), nb, (int)i, &n.out[k].t, false, false});
     }
   }
+  plan->wire = mod->trace_wire && !mod->wire_forced_off;
   if (recs.empty()) {
     *out = nullptr;
     return TK_OK;
@@ -697,6 +752,21 @@ static int build_pack_plan(tk_module* mod, const std::vector<void*>& dst, PackPl
       tk::set_error("tk_module_run_graph: overlapping record destinations");
       return TK_ERR_INVALID_ARG;
     }
+  if (plan->wire) {
+    // int32 records are coded; one that follows (in the image) a coded record of its own shape is
+    // coded as the difference from it (every bias_add after its convolution)
+    bool any = false;
+    for (size_t r = 0; r < recs.size(); ++r) {
+      Rec& c = recs[r];
+      c.wire = tk::is_int(c.t, 32) && tk::compact(c.t) && ((uintptr_t)c.src & 3) == 0;
+      any |= c.wire;
+      if (!c.wire || r == 0 || !recs[r - 1].wire) continue;
+      const tk_tensor* a = c.t;
+      const tk_tensor* b = recs[r - 1].t;
+      c.diff = a->ndim == b->ndim && std::equal(a->shape, a->shape + a->ndim, b->shape) && c.src != recs[r - 1].src;
+    }
+    plan->wire = any;
+  }
   plan->host_lo = recs.front().host;
   plan->span = recs.back().host + recs.back().bytes - plan->host_lo;
   // after node i, every record below complete_upto[i] (host order) is written
@@ -715,6 +785,7 @@ static int build_pack_plan(tk_module* mod, const std::vector<void*>& dst, PackPl
   }
   const int64_t target = std::max<int64_t>(1, (plan->span + mod->pack_chunks - 1) / mod->pack_chunks);
   std::vector<PackRecHost> table;
+  std::vector<tk::WireSegDev> wire_segs;
   int64_t cut = 0;
   size_t next_rec = 0;
   for (int i = 0; i < nn; ++i) {
@@ -723,9 +794,24 @@ static int build_pack_plan(tk_module* mod, const std::vector<void*>& dst, PackPl
     if (upto - cut < target && upto < plan->span) continue;
     PackPlan::Chunk c{i, cut, upto - cut, (int64_t)table.size(), 0, 0};
     int64_t blocks = 0;
+    PackPlan::WireChunk wc;
+    std::vector<int64_t> w_elems;
+    std::vector<int32_t> w_diff;
+    std::vector<size_t> w_rec;
+    bool in_run = false;  // the previous record of this chunk was not coded
     while (next_rec < recs.size() && recs[next_rec].host - plan->host_lo < upto) {
       const Rec& rc = recs[next_rec++];
       const int64_t off = rc.host - plan->host_lo;
+      if (rc.wire) {
+        w_elems.push_back(rc.bytes / 4), w_diff.push_back(rc.diff), w_rec.push_back(next_rec - 1);
+        in_run = false;
+        continue;
+      }
+      if (plan->wire) {
+        if (in_run) wc.raw.back().len = off + rc.bytes - wc.raw.back().off;
+        else wc.raw.push_back({off, rc.bytes});
+        in_run = true;
+      }
       const int64_t a0 = off & ~(int64_t)15;
       const int64_t nblk = (off + rc.bytes - a0 + 256 * 16 - 1) / (256 * 16);
       table.push_back({rc.src, off, rc.bytes, blocks});
@@ -735,13 +821,70 @@ static int build_pack_plan(tk_module* mod, const std::vector<void*>& dst, PackPl
     c.blocks = blocks;
     plan->chunks.push_back(c);
     cut = upto;
+    if (!plan->wire) continue;
+    if (!w_rec.empty()) {
+      std::vector<tk::WireSegRef> refs;
+      tk::wire_layout(w_elems.data(), w_diff.data(), (int)w_rec.size(), &refs, &wc.units);
+      wc.seg_off = (int64_t)wire_segs.size();
+      wc.bound = tk::wire_table_bytes((int64_t)refs.size());
+      for (const tk::WireSegRef& sr : refs) {
+        const Rec& rc = recs[w_rec[sr.rec]];
+        // a differenced record's predecessor is the record before it in the image (this chunk's
+        // or, for the chunk's first record, an earlier chunk's: decoded before this one)
+        const Rec* pv = rc.diff ? &recs[w_rec[sr.rec] - 1] : nullptr;
+        wire_segs.push_back({(const int32_t*)rc.src + sr.e0, pv ? (const int32_t*)pv->src + sr.e0 : nullptr, sr.n, 0});
+        wc.segs.push_back({rc.host + 4 * sr.e0, pv ? pv->host + 4 * sr.e0 : nullptr, sr.n});
+        wc.bound += tk::wire_seg_bound(sr.n);
+      }
+      for (int64_t nel : w_elems) wc.coded_bytes += 4 * nel;
+    }
+    plan->wchunks.push_back(std::move(wc));
   }
   if (cut != plan->span || next_rec != recs.size()) {
     tk::set_error("tk_module_run_graph: pack plan does not cover every record");
     return TK_ERR_INVALID_ARG;
   }
-  TK_HIP(hipMalloc(&plan->table, table.size() * sizeof(PackRecHost)));
-  TK_HIP(hipMemcpy(plan->table, table.data(), table.size() * sizeof(PackRecHost), hipMemcpyHostToDevice));
+  if (!table.empty()) {
+    TK_HIP(hipMalloc(&plan->table, table.size() * sizeof(PackRecHost)));
+    TK_HIP(hipMemcpy(plan->table, table.data(), table.size() * sizeof(PackRecHost), hipMemcpyHostToDevice));
+  }
+  if (plan->wire) {
+    // the device segment table, a ring of pinned slots each large enough for any chunk with every
+    // block raw, a cursor per slot, and the decode calls of every (chunk, slot) pair
+    TK_HIP(hipMalloc(&plan->wire_segs, wire_segs.size() * sizeof(tk::WireSegDev)));
+    TK_HIP(hipMemcpy(plan->wire_segs, wire_segs.data(), wire_segs.size() * sizeof(tk::WireSegDev), hipMemcpyHostToDevice));
+    int64_t slot_bytes = 0;
+    int coded_chunks = 0;
+    for (const auto& w : plan->wchunks) slot_bytes = std::max(slot_bytes, w.bound), coded_chunks += !w.segs.empty();
+    const int n_slots = std::min(3, coded_chunks);
+    for (int k = 0; k < n_slots; ++k) {
+      void* p = nullptr;
+      TK_HIP(hipHostMalloc(&p, (size_t)slot_bytes, hipHostMallocDefault));
+      plan->slots.push_back(p);
+      hipEvent_t e;
+      TK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      plan->slot_done.push_back(e);
+    }
+    plan->slot_used.assign(n_slots, 0);
+    TK_HIP(hipMalloc((void**)&plan->cursors, n_slots * sizeof(uint32_t)));
+    for (auto& w : plan->wchunks) {
+      if (w.segs.empty()) continue;
+      TK_HIP(hipEventCreateWithFlags(&w.landed, hipEventDisableTiming));
+      w.calls.reset(new PackPlan::WireCall[n_slots]);
+      for (int k = 0; k < n_slots; ++k) {
+        tk::WireJob& j = w.calls[k].job;
+        j.wire = (const char*)plan->slots[k];
+        j.wire_bytes = w.bound;
+        j.segs = w.segs.data(), j.n_seg = (int64_t)w.segs.size();
+        j.units = w.units.data(), j.n_units = (int64_t)w.units.size();
+        w.calls[k].failed = &mod->wire_failed;
+      }
+    }
+    if (!mod->wire_s) TK_HIP(hipStreamCreateWithFlags(&mod->wire_s, hipStreamNonBlocking));
+    if (!mod->dec_s) TK_HIP(hipStreamCreateWithFlags(&mod->dec_s, hipStreamNonBlocking));
+    if (!mod->wire_tail) TK_HIP(hipEventCreateWithFlags(&mod->wire_tail, hipEventDisableTiming));
+    if (!mod->decode_tail) TK_HIP(hipEventCreateWithFlags(&mod->decode_tail, hipEventDisableTiming));
+  }
   for (int m = 0; m < 2; ++m) {
     // the mirror holds the image's bytes between records (headers) from the start
     TK_HIP(hipMalloc(&plan->mirror[m], (size_t)plan->span + 16));
@@ -768,7 +911,7 @@ static int build_pack_plan(tk_module* mod, const std::vector<void*>& dst, PackPl
         rc = tk::run_node(mod->nodes[i], qs);
         if (rc) tk::set_error("node " + std::to_string(i) + ": " + tk_last_error());
       }
-      if (rc == TK_OK && has_chunk) {
+      if (rc == TK_OK && has_chunk && plan->chunks[seg].n_rec > 0) {
         const PackPlan::Chunk& ch = plan->chunks[seg];
         rc = tk::pack_records_impl((const char*)plan->table + ch.table_off * sizeof(PackRecHost), ch.n_rec, ch.blocks,
                                    plan->mirror[m], qs);
@@ -798,8 +941,52 @@ static int build_pack_plan(tk_module* mod, const std::vector<void*>& dst, PackPl
   return TK_OK;
 }
 
+// The decode host function of one chunk (decode stream): widens the chunk's slot into the image
+// on the decoder's pool and waits for it; no HIP call.
+static void wire_decode_call(void* p) {
+  auto* call = static_cast<PackPlan::WireCall*>(p);
+  if (tk::wire_decode(&call->job, 0)) call->failed->store(1);
+}
+
+// The wire side of one chunk of a packed run, after the chunk's graph and its event on s:
+//   s       graph c | ev ................ graph c+1 | ev ...
+//   wire_s  wait ev, wait slot_done[k] | cursor = 0 | encode -> slot k | raw copies | landed[c]
+//   dec_s   wait landed[c] | host function: decode slot k -> image | slot_done[k]
+static int enqueue_wire_chunk(tk_module* mod, PackPlan* plan, int m, size_t c, bool trace) {
+  const PackPlan::Chunk& ch = plan->chunks[c];
+  PackPlan::WireChunk& w = plan->wchunks[c];
+  hipStream_t ws = mod->wire_s, ds = mod->dec_s;
+  TK_HIP(hipStreamWaitEvent(ws, plan->ev[m][c], 0));
+  if (trace) TK_HIP(hipEventRecord(mod->ct_ev[2 * c], ws));
+  int k = -1;
+  if (!w.segs.empty()) {
+    k = plan->slot_next;
+    plan->slot_next = (k + 1) % (int)plan->slots.size();
+    if (plan->slot_used[k]) TK_HIP(hipStreamWaitEvent(ws, plan->slot_done[k], 0));
+    TK_HIP(hipMemsetAsync(plan->cursors + k, 0, sizeof(uint32_t), ws));
+    const int rc = tk::wire_encode_impl((const tk::WireSegDev*)plan->wire_segs + w.seg_off, (int64_t)w.segs.size(),
+                                        plan->cursors + k, plan->slots[k], w.bound, ws);
+    if (rc) return rc;
+  }
+  for (const PackPlan::Range& r : w.raw)
+    TK_HIP(hipMemcpyAsync(plan->host_lo + r.off, (char*)plan->mirror[m] + r.off, (size_t)r.len, hipMemcpyDeviceToHost, ws));
+  if (trace) {
+    TK_HIP(hipEventRecord(mod->ct_ev[2 * c + 1], ws));
+    mod->ct_bytes[c] = ch.len;
+  }
+  if (k >= 0) {
+    TK_HIP(hipEventRecord(w.landed, ws));
+    TK_HIP(hipStreamWaitEvent(ds, w.landed, 0));
+    TK_HIP(hipLaunchHostFunc(ds, wire_decode_call, &w.calls[k]));
+    TK_HIP(hipEventRecord(plan->slot_done[k], ds));
+    plan->slot_used[k] = 1;
+    w.last_slot = k;
+  }
+  return TK_OK;
+}
+
 // One packed traced run: the chunk graphs of mirror m (kernels, pack kernel) on s, each followed by
-// an event, and the chunk copies on cs, each after its event.
+// an event, and the chunk copies on cs, each after its event (wire runs: enqueue_wire_chunk).
 static int run_packed(tk_module* mod, hipStream_t s, hipStream_t cs, void* const* host_dst) {
   const size_t nd = mod->nodes.size() * TK_MAX_NODE_OUTPUTS;
   std::vector<void*> dst(host_dst, host_dst + nd);
@@ -809,6 +996,7 @@ static int run_packed(tk_module* mod, hipStream_t s, hipStream_t cs, void* const
   if (!plan) {
     if (mod->packs.size() >= 2) {  // keep the newest (a file sink alternates two images)
       TK_HIP(hipDeviceSynchronize());
+      if (mod->last_wire_plan == mod->packs.front().get()) mod->last_wire_plan = nullptr;
       mod->packs.erase(mod->packs.begin());
     }
     PackPlan* built = nullptr;
@@ -825,6 +1013,12 @@ static int run_packed(tk_module* mod, hipStream_t s, hipStream_t cs, void* const
   // the pack into mirror m waits for that mirror's last copies (two runs ago); the records the
   // kernels overwrite are only read by the packs of the previous launch on the same stream
   if (plan->mirror_used[m]) TK_HIP(hipStreamWaitEvent(s, plan->mirror_done[m], 0));
+  if (mod->wire_failed.load()) {
+    tk::set_error("tk_module_run_graph: a wire buffer of an earlier run did not decode");
+    return TK_ERR_INVALID_ARG;
+  }
+  // the encode kernels of the last wire run read the record buffers this run overwrites
+  if (mod->wire_tail_used) TK_HIP(hipStreamWaitEvent(s, mod->wire_tail, 0));
   const bool trace = mod->copy_trace;
   if (trace) {
     if (!mod->ct_t0) TK_HIP(hipEventCreate(&mod->ct_t0));
@@ -841,6 +1035,11 @@ static int run_packed(tk_module* mod, hipStream_t s, hipStream_t cs, void* const
     if (c >= plan->chunks.size()) break;  // the tail graph
     const PackPlan::Chunk& ch = plan->chunks[c];
     TK_HIP(hipEventRecord(plan->ev[m][c], s));
+    if (plan->wire) {
+      const int rc = enqueue_wire_chunk(mod, plan, m, c, trace);
+      if (rc) return rc;
+      continue;
+    }
     TK_HIP(hipStreamWaitEvent(cs, plan->ev[m][c], 0));
     if (trace) TK_HIP(hipEventRecord(mod->ct_ev[2 * c], cs));
     TK_HIP(hipMemcpyAsync(plan->host_lo + ch.off, (char*)plan->mirror[m] + ch.off, (size_t)ch.len,
@@ -850,7 +1049,20 @@ static int run_packed(tk_module* mod, hipStream_t s, hipStream_t cs, void* const
       mod->ct_bytes[c] = ch.len;
     }
   }
-  TK_HIP(hipEventRecord(plan->mirror_done[m], cs));
+  if (plan->wire) {
+    // the capture stream waits for the run's last wire work and last decode, so that capture_done
+    // (and the capture stream's synchronisation) still means "the image is complete"
+    TK_HIP(hipEventRecord(mod->wire_tail, mod->wire_s));
+    TK_HIP(hipEventRecord(plan->mirror_done[m], mod->wire_s));
+    TK_HIP(hipEventRecord(mod->decode_tail, mod->dec_s));
+    mod->wire_tail_used = true;
+    mod->last_wire_plan = plan;
+    TK_HIP(hipStreamWaitEvent(cs, mod->wire_tail, 0));
+    TK_HIP(hipStreamWaitEvent(cs, mod->decode_tail, 0));
+  } else {
+    TK_HIP(hipEventRecord(plan->mirror_done[m], cs));
+    mod->last_wire_plan = nullptr;
+  }
   plan->mirror_used[m] = true;
   TK_HIP(hipEventRecord(mod->capture_done, cs));
   mod->capture_recorded = true;
@@ -866,6 +1078,41 @@ int tk_module_set_copy_trace(tk_module* mod, int enable) {
   mod->copy_trace = enable != 0;
   mod->ct_bytes.clear();
   return TK_OK;
+}
+
+int tk_module_set_trace_wire(tk_module* mod, int enable) {
+  if (!mod || (enable != 0 && enable != 1)) {
+    tk::set_error("tk_module_set_trace_wire: invalid argument");
+    return TK_ERR_INVALID_ARG;
+  }
+  if (mod->trace_wire != (enable != 0)) mod->drop_graph();
+  mod->trace_wire = enable != 0;
+  return TK_OK;
+}
+
+int tk_module_wire_stats(tk_module* mod, double* out, int max_chunks) {
+  if (!mod || (max_chunks > 0 && !out)) {
+    tk::set_error("tk_module_wire_stats: invalid argument");
+    return TK_ERR_INVALID_ARG;
+  }
+  PackPlan* plan = mod->last_wire_plan;
+  if (!plan) return 0;
+  TK_HIP(hipEventSynchronize(mod->decode_tail));
+  if (mod->wire_failed.load()) {
+    tk::set_error("tk_module_wire_stats: a wire buffer did not decode");
+    return TK_ERR_INVALID_ARG;
+  }
+  const int n = (int)plan->wchunks.size();
+  for (int c = 0; c < n && c < max_chunks; ++c) {
+    const PackPlan::WireChunk& w = plan->wchunks[c];
+    const tk::WireJob* j = w.last_slot >= 0 ? &w.calls[w.last_slot].job : nullptr;
+    int64_t raw = 0;
+    for (const PackPlan::Range& r : w.raw) raw += r.len;
+    out[3 * c] = (double)((j ? j->used_bytes : 0) + raw);
+    out[3 * c + 1] = (double)w.coded_bytes;
+    out[3 * c + 2] = j ? j->ms : 0.0;
+  }
+  return n;
 }
 
 int tk_module_copy_trace(tk_module* mod, double* out, int max_chunks) {
@@ -1222,6 +1469,43 @@ int tk_module_tune(tk_module* mod, void* stream, int max_candidates, int reps, i
     (void)hipStreamSynchronize(s);
     (void)hipFree(flush);
   }
+  return rc;
+}
+
+int tk_wire_encode_device(const tk_wire_record* recs, int n_recs, const void* const* src, void* wire,
+                          int64_t wire_cap, void* stream) {
+  const int64_t bound = tk_wire_bound(recs, n_recs);
+  if (bound < 0) return (int)bound;
+  if (!src || !wire || wire_cap < bound) {
+    tk::set_error("tk_wire_encode_device: the wire buffer is smaller than tk_wire_bound");
+    return TK_ERR_INVALID_ARG;
+  }
+  std::vector<int64_t> n(n_recs);
+  std::vector<int32_t> d(n_recs);
+  for (int i = 0; i < n_recs; ++i) n[i] = recs[i].n_elems, d[i] = recs[i].diff != 0;
+  std::vector<tk::WireSegRef> refs;
+  std::vector<tk::WireUnit> units;
+  tk::wire_layout(n.data(), d.data(), n_recs, &refs, &units);
+  std::vector<tk::WireSegDev> segs;
+  for (const tk::WireSegRef& r : refs)
+    segs.push_back({(const int32_t*)src[r.rec] + r.e0, recs[r.rec].diff ? (const int32_t*)src[r.rec - 1] + r.e0 : nullptr,
+                    r.n, 0});
+  hipStream_t s = tk::as_stream(stream);
+  void* dev = nullptr;
+  TK_HIP(hipMalloc(&dev, segs.size() * sizeof(tk::WireSegDev) + 64));
+  uint32_t* cursor = (uint32_t*)((char*)dev + segs.size() * sizeof(tk::WireSegDev));
+  int rc = TK_OK;
+  if (hipMemcpyAsync(dev, segs.data(), segs.size() * sizeof(tk::WireSegDev), hipMemcpyHostToDevice, s) != hipSuccess ||
+      hipMemsetAsync(cursor, 0, sizeof(uint32_t), s) != hipSuccess) {
+    tk::set_error("tk_wire_encode_device: loading the segment table failed");
+    rc = TK_ERR_HIP;
+  }
+  if (rc == TK_OK) rc = tk::wire_encode_impl((const tk::WireSegDev*)dev, (int64_t)segs.size(), cursor, wire, bound, s);
+  if (hipStreamSynchronize(s) != hipSuccess && rc == TK_OK) {
+    tk::set_error("tk_wire_encode_device: the encode kernel failed");
+    rc = TK_ERR_HIP;
+  }
+  (void)hipFree(dev);
   return rc;
 }
 

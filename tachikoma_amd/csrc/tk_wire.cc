@@ -1,0 +1,346 @@
+// Host side of the trace wire format (tk_wire.h): the decoder that widens a wire buffer into the
+// trace image on a fixed thread pool, and a reference encoder so the decoder is testable without
+// a device.  Plain C++ (no HIP): also compiled alone into the sanitizer check of tools/wire_check.cc.
+#include "tk_wire.h"
+
+#include <sched.h>
+
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <condition_variable>
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <thread>
+
+#include "../../include/tachikoma.h"
+
+namespace tk {
+void set_error(const std::string& msg);
+
+void wire_layout(const int64_t* n_elems, const int32_t* diff, int n_recs, std::vector<WireSegRef>* segs,
+                 std::vector<WireUnit>* units) {
+  segs->clear();
+  units->clear();
+  int r = 0;
+  while (r < n_recs) {
+    int k = 1;  // records r .. r + k - 1 form a chain
+    while (r + k < n_recs && diff[r + k]) ++k;
+    const int64_t n = n_elems[r];
+    const int64_t S = (n + kWireSegElems - 1) / kWireSegElems;
+    const int64_t first = (int64_t)segs->size();
+    for (int m = 0; m < k; ++m)
+      for (int64_t j = 0; j < S; ++j)
+        segs->push_back({r + m, (int32_t)std::min<int64_t>(kWireSegElems, n - j * kWireSegElems), j * kWireSegElems});
+    for (int64_t j = 0; j < S; ++j) units->push_back({(int32_t)(first + j), (int32_t)S, k});
+    r += k;
+  }
+}
+
+// ---------------------------------------------------------------- thread pool
+// Sized once from the process's CPU affinity mask (never the machine's core count), at most 16;
+// TK_WIRE_THREADS overrides (1..16).  DESIGN.md section 8 has the measured rates per thread count
+// and placement.  Work items are claimed from an atomic counter; the caller waits and does not
+// decode itself (it is a HIP host-function thread).  The pool is never torn down: its threads
+// sleep between jobs and end with the process.
+namespace {
+class Pool {
+ public:
+  static Pool& get() {
+    static Pool* p = new Pool();
+    return *p;
+  }
+  int size() const { return n_; }
+  // fn(i) for i in [0, count) on up to `threads` workers; returns when all are done
+  template <typename F>
+  void run(int64_t count, int threads, F&& fn) {
+    std::lock_guard<std::mutex> job(job_mu_);  // one job at a time
+    struct Ctx {
+      F* fn;
+    } ctx{&fn};
+    {
+      std::lock_guard<std::mutex> lk(mu_);
+      call_ = [](void* c, int64_t i) { (*static_cast<Ctx*>(c)->fn)(i); };
+      ctx_ = &ctx;
+      count_ = count;
+      next_.store(0, std::memory_order_relaxed);
+      limit_ = threads > 0 ? std::min(threads, n_) : n_;
+      active_ = limit_;
+      ++gen_;
+    }
+    cv_.notify_all();
+    std::unique_lock<std::mutex> lk(mu_);
+    done_cv_.wait(lk, [&] { return active_ == 0; });
+  }
+
+ private:
+  Pool() {
+    int n = 0;
+    cpu_set_t set;
+    CPU_ZERO(&set);
+    if (sched_getaffinity(0, sizeof(set), &set) == 0) n = CPU_COUNT(&set);
+    n = std::max(1, std::min(n, 16));
+    if (const char* e = std::getenv("TK_WIRE_THREADS")) {
+      const int v = std::atoi(e);
+      if (v >= 1 && v <= 16) n = v;
+    }
+    n_ = n;
+    for (int t = 0; t < n_; ++t) std::thread([this, t] { worker(t); }).detach();
+  }
+  void worker(int id) {
+    uint64_t seen = 0;
+    for (;;) {
+      void (*call)(void*, int64_t);
+      void* ctx;
+      int64_t count;
+      {
+        std::unique_lock<std::mutex> lk(mu_);
+        cv_.wait(lk, [&] { return gen_ != seen; });
+        seen = gen_;
+        if (id >= limit_) continue;
+        call = call_, ctx = ctx_, count = count_;
+      }
+      for (int64_t i; (i = next_.fetch_add(1, std::memory_order_relaxed)) < count;) call(ctx, i);
+      std::lock_guard<std::mutex> lk(mu_);
+      if (--active_ == 0) done_cv_.notify_all();
+    }
+  }
+  int n_ = 1;
+  std::mutex job_mu_, mu_;
+  std::condition_variable cv_, done_cv_;
+  uint64_t gen_ = 0;
+  void (*call_)(void*, int64_t) = nullptr;
+  void* ctx_ = nullptr;
+  int64_t count_ = 0;
+  int limit_ = 0, active_ = 0;
+  std::atomic<int64_t> next_{0};
+};
+
+// ---------------------------------------------------------------- decoder
+// image words are read and written through memcpy: NDArray-list payload offsets are 8-byte
+// aligned only by layout, and the decoder promises nothing about alignment at all
+template <int W, bool D>
+void widen(char* dst, const char* prev, const uint8_t* p, int cnt, uint32_t base) {
+  for (int i = 0; i < cnt; ++i) {
+    uint32_t v = base;
+    if (W >= 1) v += p[i];
+    if (W >= 2) v += (uint32_t)p[cnt + i] << 8;
+    if (W >= 3) v += (uint32_t)p[2 * cnt + i] << 16;
+    if (W >= 4) v += (uint32_t)p[3 * cnt + i] << 24;
+    if (D) {
+      uint32_t q;
+      std::memcpy(&q, prev + 4 * (int64_t)i, 4);
+      v += q;
+    }
+    std::memcpy(dst + 4 * (int64_t)i, &v, 4);
+  }
+}
+template <bool D>
+void widen_w(int w, char* dst, const char* prev, const uint8_t* p, int cnt, uint32_t base) {
+  switch (w) {
+    case 0: return widen<0, D>(dst, prev, p, cnt, base);
+    case 1: return widen<1, D>(dst, prev, p, cnt, base);
+    case 2: return widen<2, D>(dst, prev, p, cnt, base);
+    case 3: return widen<3, D>(dst, prev, p, cnt, base);
+    default: return widen<4, D>(dst, prev, p, cnt, base);
+  }
+}
+
+// Decodes segment i; returns its length rounded to 64 B, or -1 if it does not lie inside the
+// payload (nothing past the payload is read, nothing outside the segment's record is written).
+int64_t decode_seg(const WireJob& j, int64_t i, const char* payload, int64_t payload_bytes) {
+  const WireSegHost& sg = j.segs[i];
+  uint32_t start;
+  std::memcpy(&start, j.wire + 4 * i, 4);
+  const int64_t off = (int64_t)start * 64;
+  const int nb = (sg.n + kWireBlock - 1) / kWireBlock;
+  const int64_t hdr = wire_header_bytes(nb);
+  if (off > payload_bytes || hdr > payload_bytes - off) return -1;
+  const char* p = payload + off;
+  const uint8_t* widths = (const uint8_t*)p + wire_align(4 * (int64_t)nb, 16);
+  int64_t len = hdr;
+  for (int b = 0; b < nb; ++b) {
+    if (widths[b] > 4) return -1;
+    len += (int64_t)widths[b] * std::min(kWireBlock, sg.n - b * kWireBlock);
+  }
+  if (len > payload_bytes - off) return -1;
+  const uint8_t* q = (const uint8_t*)p + hdr;
+  for (int b = 0; b < nb; ++b) {
+    const int cnt = std::min(kWireBlock, sg.n - b * kWireBlock);
+    const int w = widths[b];
+    int32_t base;
+    std::memcpy(&base, p + 4 * b, 4);
+    char* dst = sg.dst + 4 * (int64_t)b * kWireBlock;
+    if (sg.prev) widen_w<true>(w, dst, sg.prev + 4 * (int64_t)b * kWireBlock, q, cnt, (uint32_t)base);
+    else widen_w<false>(w, dst, nullptr, q, cnt, (uint32_t)base);
+    q += (int64_t)w * cnt;
+  }
+  return wire_align(len, 64);
+}
+}  // namespace
+
+int wire_pool_threads() { return Pool::get().size(); }
+
+int wire_decode(WireJob* job, int threads) {
+  const auto t0 = std::chrono::steady_clock::now();
+  job->status = 0;
+  job->used_bytes = 0;
+  const int64_t table = wire_table_bytes(job->n_seg);
+  if (job->n_seg < 0 || !job->wire || job->wire_bytes < table) {
+    job->status = TK_ERR_INVALID_ARG;
+    return job->status;
+  }
+  std::atomic<int64_t> used{table};
+  std::atomic<int> bad{0};
+  const char* payload = job->wire + table;
+  const int64_t payload_bytes = job->wire_bytes - table;
+  Pool::get().run(job->n_units, threads, [&](int64_t u) {
+    const WireUnit& un = job->units[u];
+    int64_t sum = 0;
+    for (int m = 0; m < un.count; ++m) {
+      const int64_t r = decode_seg(*job, un.first + (int64_t)m * un.stride, payload, payload_bytes);
+      if (r < 0) {
+        bad.store(1, std::memory_order_relaxed);
+        break;  // what follows in the chain would be added to undecoded bytes
+      }
+      sum += r;
+    }
+    used.fetch_add(sum, std::memory_order_relaxed);
+  });
+  job->used_bytes = used.load();
+  job->status = bad.load() ? TK_ERR_INVALID_ARG : 0;
+  job->ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return job->status;
+}
+
+// ---------------------------------------------------------------- reference encoder
+namespace {
+// one segment at `out`; returns its unrounded length
+int64_t encode_seg(const char* src, const char* prev, int n, char* out) {
+  const int nb = (n + kWireBlock - 1) / kWireBlock;
+  const int64_t hdr = wire_header_bytes(nb);
+  std::memset(out, 0, (size_t)hdr);
+  uint8_t* widths = (uint8_t*)out + wire_align(4 * (int64_t)nb, 16);
+  uint8_t* q = (uint8_t*)out + hdr;
+  for (int b = 0; b < nb; ++b) {
+    const int cnt = std::min(kWireBlock, n - b * kWireBlock);
+    int32_t v[kWireBlock];
+    for (int i = 0; i < cnt; ++i) {
+      uint32_t a, pv = 0;
+      std::memcpy(&a, src + 4 * ((int64_t)b * kWireBlock + i), 4);
+      if (prev) std::memcpy(&pv, prev + 4 * ((int64_t)b * kWireBlock + i), 4);
+      v[i] = (int32_t)(a - pv);
+    }
+    const int32_t mn = *std::min_element(v, v + cnt), mx = *std::max_element(v, v + cnt);
+    const uint32_t range = (uint32_t)mx - (uint32_t)mn;  // exact: mx >= mn as signed values
+    const int w = range == 0 ? 0 : range <= 0xFFu ? 1 : range <= 0xFFFFu ? 2 : range <= 0xFFFFFFu ? 3 : 4;
+    std::memcpy(out + 4 * b, &mn, 4);
+    widths[b] = (uint8_t)w;
+    for (int k = 0; k < w; ++k)
+      for (int i = 0; i < cnt; ++i) q[k * cnt + i] = (uint8_t)(((uint32_t)v[i] - (uint32_t)mn) >> (8 * k));
+    q += (int64_t)w * cnt;
+  }
+  return (char*)q - out;
+}
+
+struct HostPlan {
+  std::vector<WireSegRef> segs;
+  std::vector<WireUnit> units;
+  int64_t bound = 0;
+};
+int host_plan(const tk_wire_record* recs, int n_recs, int64_t image_bytes, HostPlan* p, const char* who) {
+  if (!recs || n_recs < 1) {
+    set_error(std::string(who) + ": no records");
+    return TK_ERR_INVALID_ARG;
+  }
+  std::vector<int64_t> n(n_recs);
+  std::vector<int32_t> d(n_recs);
+  for (int i = 0; i < n_recs; ++i) {
+    n[i] = recs[i].n_elems;
+    d[i] = recs[i].diff != 0;
+    const bool inside = recs[i].offset >= 0 && recs[i].n_elems >= 1 && recs[i].n_elems <= ((int64_t)1 << 40) &&
+                        (image_bytes < 0 || (recs[i].offset <= image_bytes && 4 * recs[i].n_elems <= image_bytes - recs[i].offset));
+    if (!inside || (d[i] && (i == 0 || recs[i - 1].n_elems != recs[i].n_elems))) {
+      set_error(std::string(who) + ": record " + std::to_string(i) +
+                " lies outside the image or is differenced against a record of another size");
+      return TK_ERR_INVALID_ARG;
+    }
+  }
+  wire_layout(n.data(), d.data(), n_recs, &p->segs, &p->units);
+  p->bound = wire_table_bytes((int64_t)p->segs.size());
+  for (const WireSegRef& s : p->segs) p->bound += wire_seg_bound(s.n);
+  return TK_OK;
+}
+}  // namespace
+}  // namespace tk
+
+extern "C" {
+
+int64_t tk_wire_bound(const tk_wire_record* recs, int n_recs) {
+  tk::HostPlan p;
+  const int rc = tk::host_plan(recs, n_recs, -1, &p, "tk_wire_bound");
+  return rc ? rc : p.bound;
+}
+
+int64_t tk_wire_encode_host(const tk_wire_record* recs, int n_recs, const void* image, int64_t image_bytes,
+                            void* wire, int64_t wire_cap) {
+  tk::HostPlan p;
+  const int rc = tk::host_plan(recs, n_recs, image_bytes, &p, "tk_wire_encode_host");
+  if (rc) return rc;
+  if (!image || !wire || wire_cap < p.bound) {
+    tk::set_error("tk_wire_encode_host: the wire buffer is smaller than tk_wire_bound");
+    return TK_ERR_INVALID_ARG;
+  }
+  const int64_t table = tk::wire_table_bytes((int64_t)p.segs.size());
+  std::memset(wire, 0, (size_t)table);
+  char* payload = (char*)wire + table;
+  int64_t cursor = 0;
+  for (size_t i = 0; i < p.segs.size(); ++i) {
+    const tk::WireSegRef& s = p.segs[i];
+    const char* src = (const char*)image + recs[s.rec].offset + 4 * s.e0;
+    const char* prev = recs[s.rec].diff ? (const char*)image + recs[s.rec - 1].offset + 4 * s.e0 : nullptr;
+    const uint32_t start = (uint32_t)(cursor / 64);
+    std::memcpy((char*)wire + 4 * i, &start, 4);
+    const int64_t len = tk::encode_seg(src, prev, s.n, payload + cursor);
+    const int64_t padded = tk::wire_align(len, 64);
+    std::memset(payload + cursor + len, 0, (size_t)(padded - len));
+    cursor += padded;
+  }
+  return table + cursor;
+}
+
+int tk_wire_decode(const tk_wire_record* recs, int n_recs, const void* wire, int64_t wire_bytes, void* image,
+                   int64_t image_bytes, int threads) {
+  tk::HostPlan p;
+  const int rc = tk::host_plan(recs, n_recs, image_bytes, &p, "tk_wire_decode");
+  if (rc) return rc;
+  if (!wire || !image || wire_bytes < 0) {
+    tk::set_error("tk_wire_decode: null buffer");
+    return TK_ERR_INVALID_ARG;
+  }
+  std::vector<tk::WireSegHost> segs(p.segs.size());
+  for (size_t i = 0; i < p.segs.size(); ++i) {
+    const tk::WireSegRef& s = p.segs[i];
+    segs[i].dst = (char*)image + recs[s.rec].offset + 4 * s.e0;
+    segs[i].prev = recs[s.rec].diff ? (const char*)image + recs[s.rec - 1].offset + 4 * s.e0 : nullptr;
+    segs[i].n = s.n;
+  }
+  tk::WireJob job;
+  job.wire = (const char*)wire;
+  job.wire_bytes = wire_bytes;
+  job.segs = segs.data();
+  job.n_seg = (int64_t)segs.size();
+  job.units = p.units.data();
+  job.n_units = (int64_t)p.units.size();
+  if (tk::wire_decode(&job, threads)) {
+    tk::set_error("tk_wire_decode: the segment table or a segment does not lie inside the wire buffer");
+    return TK_ERR_INVALID_ARG;
+  }
+  return TK_OK;
+}
+
+int tk_wire_threads(void) { return tk::wire_pool_threads(); }
+
+}  // extern "C"

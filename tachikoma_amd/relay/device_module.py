@@ -1013,6 +1013,22 @@ class DeviceModule:
         _lib.check(min(self.lib.tk_module_copy_trace(self.handle, buf, n), 0), "tk_module_copy_trace")
         return [{"bytes": int(buf[3 * c]), "start_ms": buf[3 * c + 1], "end_ms": buf[3 * c + 2]} for c in range(n)]
 
+    def set_trace_wire(self, enable: bool) -> None:
+        """Trace wire of the packed capture: int32 records cross the link narrowed and are widened
+        on the host (tk_module_set_trace_wire; on by default, TK_TRACE_WIRE=0 forces it off)."""
+        _lib.check(self.lib.tk_module_set_trace_wire(self.handle, int(enable)), "tk_module_set_trace_wire")
+
+    def wire_stats(self) -> List[dict]:
+        """Per chunk of the last wire run: bytes that crossed the link, raw bytes of the coded
+        records, host decode ms (tk_module_wire_stats; waits for the decodes).  Empty when the last
+        traced run was not a wire run."""
+        n = self.lib.tk_module_wire_stats(self.handle, None, 0)
+        _lib.check(min(n, 0), "tk_module_wire_stats")
+        buf = (ctypes.c_double * max(1, 3 * n))()
+        _lib.check(min(self.lib.tk_module_wire_stats(self.handle, buf, n), 0), "tk_module_wire_stats")
+        return [{"wire_bytes": int(buf[3 * c]), "coded_raw_bytes": int(buf[3 * c + 1]), "decode_ms": buf[3 * c + 2]}
+                for c in range(n)]
+
     def set_profiling(self, enable: bool) -> None:
         _lib.check(self.lib.tk_module_set_profiling(self.handle, int(enable)), "tk_module_set_profiling")
 
