@@ -663,7 +663,11 @@ int tk_module_set_copy_trace(tk_module* mod, int enable);
 int tk_module_copy_trace(tk_module* mod, double* out, int max_chunks);
 /* Trace wire (packed capture only; host-issued runs and graph copy modes 1..5 stay raw): with
  * wire on (the default; TK_TRACE_WIRE=0 in the environment at tk_module_create forces it off),
- * int32 records do not cross the link as they are.  After each chunk's graph an encode kernel on
+ * int32 records do not cross the link as they are, and neither do 1-byte records that their node
+ * declares as the clip of the record directly before them in the image (same dtype and shape: the
+ * clip output of a conv, dense or add block, or a TK_NODE_CLIP of the preceding record): those are
+ * coded as clamps of that record (format below; TK_WIRE_CLAMP=0 in the environment at
+ * tk_module_create keeps them raw).  After each chunk's graph an encode kernel on
  * a module-owned wire stream reads them from their own device buffers and writes the wire format
  * below straight into a pinned host slot (a ring of three worst-case-sized chunk slots); the
  * other records still go through the mirror, copied in runs of adjacent records on the wire
@@ -684,7 +688,16 @@ int tk_module_wire_stats(tk_module* mod, double* out, int max_chunks);
  * coded as an int32 base (the block minimum) plus offsets of 0..4 bytes each, in byte planes;
  * a record with diff != 0 is coded as its wrap-around difference from the record before it, which
  * must have the same element count.  `offset` is the record's byte offset in the trace image
- * (any alignment).  tk_wire_bound: the worst-case wire size.  tk_wire_encode_host: the reference
+ * (any alignment).  `kind` is the element kind: 0 int32 (the above), 1 int8, 2 uint8.  A 1-byte
+ * record keeps the geometry (256-element blocks, 64-block segments, base[nb] / width[nb] header)
+ * with `offset` / `n_elems` counting bytes and two block forms: width 0 is a constant block (the
+ * value in byte 0 of the base), width 1 one raw plane of the record's own bytes.  With diff != 0 a
+ * 1-byte record is clamp-predicted from the record before it (same kind and element count): width
+ * 0 then means block == clamp(predecessor's block, lo, hi), lo / hi being the block's own minimum /
+ * maximum in the record's dtype, stored in base bytes 0 / 1, and width 1 is still the raw plane
+ * (the escape of a block the clamp does not reproduce), so any data round-trips; the decoder reads
+ * the predecessor from image bytes already present and refuses other widths.  One buffer may mix
+ * kinds.  tk_wire_bound: the worst-case wire size.  tk_wire_encode_host: the reference
  * encoder (reads the records from `image`), returns the wire bytes written.  tk_wire_decode:
  * widens `wire` into `image` on up to `threads` pool threads (<= 0: the pool, which is sized from
  * the CPU affinity mask, at most 16, TK_WIRE_THREADS overrides; tk_wire_threads reports it); a
@@ -696,7 +709,7 @@ typedef struct {
   int64_t offset;
   int64_t n_elems;
   int32_t diff;
-  int32_t reserved;
+  int32_t kind;
 } tk_wire_record;
 int64_t tk_wire_bound(const tk_wire_record* recs, int n_recs);
 int64_t tk_wire_encode_host(const tk_wire_record* recs, int n_recs, const void* image, int64_t image_bytes,

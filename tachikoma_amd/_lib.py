@@ -312,7 +312,7 @@ class tk_wire_record(ctypes.Structure):
         ("offset", ctypes.c_int64),
         ("n_elems", ctypes.c_int64),
         ("diff", ctypes.c_int32),
-        ("reserved", ctypes.c_int32),
+        ("kind", ctypes.c_int32),      # 0 int32, 1 int8, 2 uint8
     ]
 
 

@@ -707,6 +707,14 @@ int pack_records_impl(const void* table, int nrec, int64_t blocks, void* mirror,
 // (it cannot: the buffer is sized for every block raw), and the decoder then refuses the entry.
 // The buffer is usually a pinned host slot: every store to it is a full 16-byte plane piece, a
 // header word, or (last, short block of a record only) a byte.
+//
+// 1-byte segments (kind int8 / uint8) keep the geometry: a lane's 16 elements are one 16-byte load
+// of the record and, for a clamp-predicted record, one of its predecessor.  Bytes are compared as
+// uint8 (int8 with the sign bit flipped); the butterfly gives the block's lo and hi, every lane
+// tests clamp(prev, lo, hi) == src on its 16 bytes and a 16-lane AND decides between width 0 and
+// the raw plane, which is the lane's 16 loaded bytes stored as they are.
+__device__ __forceinline__ uint32_t wire_byte(const uint32_t* w, int j) { return (w[j >> 2] >> (8 * (j & 3))) & 0xFFu; }
+
 __global__ __launch_bounds__(256) void wire_encode_kernel(const WireSegDev* __restrict__ segs, uint32_t* cursor,
                                                           uint32_t* __restrict__ table, uint8_t* __restrict__ payload,
                                                           uint32_t cap_units) {
@@ -719,53 +727,108 @@ __global__ __launch_bounds__(256) void wire_encode_kernel(const WireSegDev* __re
   const int nb = (n + kWireBlock - 1) / kWireBlock;
   const int g = threadIdx.x >> 4, l = threadIdx.x & 15;
   const bool aligned = ((((uintptr_t)sg.src) | ((uintptr_t)sg.prev)) & 15) == 0;
-  uint32_t v[4][16];
+  const bool bytes = sg.kind != kWireI32;
+  const int32_t* src32 = static_cast<const int32_t*>(sg.src);
+  const int32_t* prev32 = static_cast<const int32_t*>(sg.prev);
+  uint32_t v[4][16];  // 1-byte segments: v[p][0..3] are the lane's 16 bytes as loaded
+  if (bytes) {
+    const uint8_t* src8 = static_cast<const uint8_t*>(sg.src);
+    const uint8_t* prev8 = static_cast<const uint8_t*>(sg.prev);
+    const uint32_t flip = sg.kind == kWireI8 ? 0x80u : 0u;
 #pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    const int b = p * 16 + g;
-    const int e0 = b * kWireBlock + l * 16;
-    int32_t mn = INT_MAX, mx = INT_MIN;
-    if (aligned && e0 + 16 <= n) {
+    for (int p = 0; p < 4; ++p) {
+      const int b = p * 16 + g;
+      const int e0 = b * kWireBlock + l * 16;
+      const int valid = min(16, n - e0);  // <= 0: the lane holds nothing
+      uint32_t pv[4] = {0, 0, 0, 0};
+      if (aligned && valid == 16) {
+        const tk_v4i a = *reinterpret_cast<const tk_v4i*>(src8 + e0);
+        v[p][0] = (uint32_t)a.x, v[p][1] = (uint32_t)a.y, v[p][2] = (uint32_t)a.z, v[p][3] = (uint32_t)a.w;
+        if (prev8) {
+          const tk_v4i c = *reinterpret_cast<const tk_v4i*>(prev8 + e0);
+          pv[0] = (uint32_t)c.x, pv[1] = (uint32_t)c.y, pv[2] = (uint32_t)c.z, pv[3] = (uint32_t)c.w;
+        }
+      } else {
+        v[p][0] = v[p][1] = v[p][2] = v[p][3] = 0;
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const tk_v4i a = *reinterpret_cast<const tk_v4i*>(sg.src + e0 + 4 * q);
-        v[p][4 * q] = (uint32_t)a.x, v[p][4 * q + 1] = (uint32_t)a.y, v[p][4 * q + 2] = (uint32_t)a.z,
-                 v[p][4 * q + 3] = (uint32_t)a.w;
+        for (int j = 0; j < 16; ++j)
+          if (j < valid) {
+            v[p][j >> 2] |= (uint32_t)src8[e0 + j] << (8 * (j & 3));
+            if (prev8) pv[j >> 2] |= (uint32_t)prev8[e0 + j] << (8 * (j & 3));
+          }
       }
-      if (sg.prev) {
+      uint32_t lo = 0xFFu, hi = 0u;  // in the flipped (unsigned) order
+#pragma unroll
+      for (int j = 0; j < 16; ++j)
+        if (j < valid) {
+          const uint32_t x = wire_byte(v[p], j) ^ flip;
+          lo = min(lo, x), hi = max(hi, x);
+        }
+#pragma unroll
+      for (int m = 8; m >= 1; m >>= 1) {
+        lo = min(lo, (uint32_t)__shfl_xor((int)lo, m, 16));
+        hi = max(hi, (uint32_t)__shfl_xor((int)hi, m, 16));
+      }
+      int coded = 0;
+      if (prev8) {  // the same for the whole workgroup: every lane takes part in the AND
+        coded = 1;
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+          if (j < valid) coded &= min(max(wire_byte(pv, j) ^ flip, lo), hi) == (wire_byte(v[p], j) ^ flip);
+#pragma unroll
+        for (int m = 8; m >= 1; m >>= 1) coded &= __shfl_xor(coded, m, 16);
+      }
+      coded |= lo == hi;
+      if (l == 0 && b < nb) s_base[b] = (int32_t)((lo ^ flip) | ((hi ^ flip) << 8)), s_w[b] = coded ? 0u : 1u;
+    }
+  } else {
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      const int b = p * 16 + g;
+      const int e0 = b * kWireBlock + l * 16;
+      int32_t mn = INT_MAX, mx = INT_MIN;
+      if (aligned && e0 + 16 <= n) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          const tk_v4i a = *reinterpret_cast<const tk_v4i*>(sg.prev + e0 + 4 * q);
-          v[p][4 * q] -= (uint32_t)a.x, v[p][4 * q + 1] -= (uint32_t)a.y, v[p][4 * q + 2] -= (uint32_t)a.z,
-              v[p][4 * q + 3] -= (uint32_t)a.w;
+          const tk_v4i a = *reinterpret_cast<const tk_v4i*>(src32 + e0 + 4 * q);
+          v[p][4 * q] = (uint32_t)a.x, v[p][4 * q + 1] = (uint32_t)a.y, v[p][4 * q + 2] = (uint32_t)a.z,
+                   v[p][4 * q + 3] = (uint32_t)a.w;
+        }
+        if (prev32) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const tk_v4i a = *reinterpret_cast<const tk_v4i*>(prev32 + e0 + 4 * q);
+            v[p][4 * q] -= (uint32_t)a.x, v[p][4 * q + 1] -= (uint32_t)a.y, v[p][4 * q + 2] -= (uint32_t)a.z,
+                v[p][4 * q + 3] -= (uint32_t)a.w;
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < 16; ++j) mn = min(mn, (int32_t)v[p][j]), mx = max(mx, (int32_t)v[p][j]);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+          uint32_t x = 0;
+          if (e0 + j < n) {
+            x = (uint32_t)src32[e0 + j];
+            if (prev32) x -= (uint32_t)prev32[e0 + j];
+            mn = min(mn, (int32_t)x), mx = max(mx, (int32_t)x);
+          }
+          v[p][j] = x;
         }
       }
 #pragma unroll
-      for (int j = 0; j < 16; ++j) mn = min(mn, (int32_t)v[p][j]), mx = max(mx, (int32_t)v[p][j]);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        uint32_t x = 0;
-        if (e0 + j < n) {
-          x = (uint32_t)sg.src[e0 + j];
-          if (sg.prev) x -= (uint32_t)sg.prev[e0 + j];
-          mn = min(mn, (int32_t)x), mx = max(mx, (int32_t)x);
-        }
-        v[p][j] = x;
+      for (int m = 8; m >= 1; m >>= 1) {
+        mn = min(mn, __shfl_xor(mn, m, 16));
+        mx = max(mx, __shfl_xor(mx, m, 16));
       }
-    }
+      // exact in unsigned arithmetic (mx >= mn as signed values): INT_MIN and INT_MAX in one block
+      // give 2^32 - 1 and the raw width, not a wrapped range
+      const uint32_t range = (uint32_t)mx - (uint32_t)mn;
+      const uint32_t w = range == 0 ? 0 : range <= 0xFFu ? 1 : range <= 0xFFFFu ? 2 : range <= 0xFFFFFFu ? 3 : 4;
+      if (l == 0 && b < nb) s_base[b] = mn, s_w[b] = w;
 #pragma unroll
-    for (int m = 8; m >= 1; m >>= 1) {
-      mn = min(mn, __shfl_xor(mn, m, 16));
-      mx = max(mx, __shfl_xor(mx, m, 16));
+      for (int j = 0; j < 16; ++j) v[p][j] -= (uint32_t)mn;
     }
-    // exact in unsigned arithmetic (mx >= mn as signed values): INT_MIN and INT_MAX in one block
-    // give 2^32 - 1 and the raw width, not a wrapped range
-    const uint32_t range = (uint32_t)mx - (uint32_t)mn;
-    const uint32_t w = range == 0 ? 0 : range <= 0xFFu ? 1 : range <= 0xFFFFu ? 2 : range <= 0xFFFFFFu ? 3 : 4;
-    if (l == 0 && b < nb) s_base[b] = mn, s_w[b] = w;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) v[p][j] -= (uint32_t)mn;
   }
   __syncthreads();
   const uint32_t base_bytes = (uint32_t)((4 * nb + 15) & ~15);
@@ -803,6 +866,18 @@ __global__ __launch_bounds__(256) void wire_encode_kernel(const WireSegDev* __re
     const int cnt = min(kWireBlock, n - b * kWireBlock);
     const uint32_t w = s_w[b];
     uint8_t* q = out + s_off[b];
+    if (bytes) {
+      if (w == 0) continue;
+      if (cnt == kWireBlock) {
+        __builtin_nontemporal_store(tk_v4i{(int)v[p][0], (int)v[p][1], (int)v[p][2], (int)v[p][3]},
+                                    reinterpret_cast<tk_v4i*>(q + l * 16));
+      } else {
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+          if (l * 16 + j < cnt) q[l * 16 + j] = (uint8_t)wire_byte(v[p], j);
+      }
+      continue;
+    }
     for (uint32_t k = 0; k < w; ++k) {
       const uint32_t sh = 8 * k;
       uint32_t o[4];

@@ -273,8 +273,9 @@ struct PackPlan {
   std::vector<hipGraph_t> g[2];   // per mirror: one graph per chunk (+ a tail graph)
   std::vector<hipGraphExec_t> ge[2];
   int next = 0;
-  // Trace wire (tk_module_set_trace_wire): the int32 records of a chunk are not packed; an encode
-  // kernel writes them into a pinned slot and a host function widens the slot into the image.
+  // Trace wire (tk_module_set_trace_wire): the int32 records of a chunk, and its 1-byte records that
+  // are clips of the record before them, are not packed; an encode kernel writes them into a pinned
+  // slot and a host function widens the slot into the image.
   bool wire = false;
   struct Range {
     int64_t off, len;
@@ -363,7 +364,8 @@ struct tk_module {
   std::vector<int64_t> ct_bytes;
   // trace wire of the packed capture: on unless TK_TRACE_WIRE=0 was set when the module was
   // created; wire traffic and decodes run on two streams of the module's own
-  bool trace_wire = true, wire_forced_off = false;
+  // TK_WIRE_CLAMP=0 at creation keeps the clip records raw (the same library's comparison run)
+  bool trace_wire = true, wire_forced_off = false, wire_clamp = true;
   hipStream_t wire_s = nullptr, dec_s = nullptr;
   hipEvent_t wire_tail = nullptr, decode_tail = nullptr;  // last wire work / decode of the last wire run
   bool wire_tail_used = false;
@@ -532,6 +534,7 @@ int tk_module_create(const tk_node* nodes, int n_nodes, tk_module** out) {
   }
   auto mod = std::make_unique<tk_module>();
   if (const char* e = std::getenv("TK_TRACE_WIRE")) mod->wire_forced_off = e[0] == '0' && e[1] == 0;
+  if (const char* e = std::getenv("TK_WIRE_CLAMP")) mod->wire_clamp = !(e[0] == '0' && e[1] == 0);
   mod->nodes.resize(n_nodes);
   for (int i = 0; i < n_nodes; ++i) {
     const tk_node& src = nodes[i];
@@ -728,9 +731,18 @@ static int build_pack_plan(tk_module* mod, const std::vector<void*>& dst, PackPl
     char* host;
     const void* src;
     int64_t bytes;
-    int node;
+    int node, out;
     const tk_tensor* t;
     bool wire, diff;  // coded on the wire; as the difference from the record before it
+    bool clamp;       // coded on the wire as a clamp of the record before it (1-byte)
+  };
+  // the tensor that output k of node n clips, where the node declares that output as a clip
+  auto clip_input = [](const tk::Node& n, int k) -> const void* {
+    const tk_node& d = n.desc;
+    const bool block = d.kind == TK_NODE_CONV_BLOCK || d.kind == TK_NODE_DENSE_BLOCK;
+    if ((block && d.attrs.block.has_clip) || (d.kind == TK_NODE_ADD_BLOCK && d.attrs.add_block.has_clip))
+      return k >= 1 && k == d.n_outputs - 1 ? tk::ptr(&n.out[k - 1].t) : nullptr;
+    return d.kind == TK_NODE_CLIP && k == 0 ? tk::ptr(&n.in[0].t) : nullptr;
   };
   std::vector<Rec> recs;
   for (size_t i = 0; i < mod->nodes.size(); ++i) {
@@ -738,7 +750,7 @@ static int build_pack_plan(tk_module* mod, const std::vector<void*>& dst, PackPl
     for (int k = 0; k < n.desc.n_outputs; ++k) {
       char* h = (char*)dst[i * TK_MAX_NODE_OUTPUTS + k];
       const int64_t nb = tk::nbytes(&n.out[k].t);
-      if (h && nb > 0) recs.push_back({h, tk::ptr(&n.out[k].t), nb, (int)i, &n.out[k].t, false, false});
+      if (h && nb > 0) recs.push_back({h, tk::ptr(&n.out[k].t), nb, (int)i, k, &n.out[k].t, false, false, false});
     }
   }
   plan->wire = mod->trace_wire && !mod->wire_forced_off;
@@ -754,16 +766,25 @@ static int build_pack_plan(tk_module* mod, const std::vector<void*>& dst, PackPl
     }
   if (plan->wire) {
     // int32 records are coded; one that follows (in the image) a coded record of its own shape is
-    // coded as the difference from it (every bias_add after its convolution)
+    // coded as the difference from it (every bias_add after its convolution).  A compact 1-byte
+    // record that its node declares as the clip of the record before it in the image (same dtype
+    // and shape) is coded as a clamp of that record; every other 1-byte record stays raw.
     bool any = false;
     for (size_t r = 0; r < recs.size(); ++r) {
       Rec& c = recs[r];
+      const tk_tensor* a = c.t;
+      const tk_tensor* b = r ? recs[r - 1].t : nullptr;
+      const bool same_shape = b && a->ndim == b->ndim && std::equal(a->shape, a->shape + a->ndim, b->shape);
+      if (mod->wire_clamp && tk::is_int8ish(a) && tk::compact(a) && same_shape && tk::compact(b) &&
+          a->dtype.code == b->dtype.code && b->dtype.bits == 8 && b->dtype.lanes == 1 && c.src != recs[r - 1].src &&
+          clip_input(mod->nodes[c.node], c.out) == recs[r - 1].src) {
+        c.wire = c.clamp = any = true;
+        continue;
+      }
       c.wire = tk::is_int(c.t, 32) && tk::compact(c.t) && ((uintptr_t)c.src & 3) == 0;
       any |= c.wire;
       if (!c.wire || r == 0 || !recs[r - 1].wire) continue;
-      const tk_tensor* a = c.t;
-      const tk_tensor* b = recs[r - 1].t;
-      c.diff = a->ndim == b->ndim && std::equal(a->shape, a->shape + a->ndim, b->shape) && c.src != recs[r - 1].src;
+      c.diff = same_shape && tk::is_int(b, 32) && c.src != recs[r - 1].src;
     }
     plan->wire = any;
   }
@@ -803,7 +824,10 @@ static int build_pack_plan(tk_module* mod, const std::vector<void*>& dst, PackPl
       const Rec& rc = recs[next_rec++];
       const int64_t off = rc.host - plan->host_lo;
       if (rc.wire) {
-        w_elems.push_back(rc.bytes / 4), w_diff.push_back(rc.diff), w_rec.push_back(next_rec - 1);
+        // a clamp-coded record follows its predecessor in the decode order only where that one is
+        // coded in this chunk too (a clamp of a clamp); a raw predecessor has landed by then
+        const bool chained = rc.diff || (rc.clamp && !w_rec.empty() && w_rec.back() == next_rec - 2);
+        w_elems.push_back(rc.bytes / tk::elem_bytes(rc.t)), w_diff.push_back(chained), w_rec.push_back(next_rec - 1);
         in_run = false;
         continue;
       }
@@ -831,12 +855,15 @@ static int build_pack_plan(tk_module* mod, const std::vector<void*>& dst, PackPl
         const Rec& rc = recs[w_rec[sr.rec]];
         // a differenced record's predecessor is the record before it in the image (this chunk's
         // or, for the chunk's first record, an earlier chunk's: decoded before this one)
-        const Rec* pv = rc.diff ? &recs[w_rec[sr.rec] - 1] : nullptr;
-        wire_segs.push_back({(const int32_t*)rc.src + sr.e0, pv ? (const int32_t*)pv->src + sr.e0 : nullptr, sr.n, 0});
-        wc.segs.push_back({rc.host + 4 * sr.e0, pv ? pv->host + 4 * sr.e0 : nullptr, sr.n});
-        wc.bound += tk::wire_seg_bound(sr.n);
+        const Rec* pv = rc.diff || rc.clamp ? &recs[w_rec[sr.rec] - 1] : nullptr;
+        const int esize = tk::elem_bytes(rc.t);
+        const int kind = esize == 4 ? tk::kWireI32 : tk::is_int(rc.t, 8) ? tk::kWireI8 : tk::kWireU8;
+        const int64_t e0 = esize * sr.e0;
+        wire_segs.push_back({(const char*)rc.src + e0, pv ? (const char*)pv->src + e0 : nullptr, sr.n, kind});
+        wc.segs.push_back({rc.host + e0, pv ? pv->host + e0 : nullptr, sr.n, kind});
+        wc.bound += tk::wire_seg_bound(sr.n, esize);
       }
-      for (int64_t nel : w_elems) wc.coded_bytes += 4 * nel;
+      for (size_t q : w_rec) wc.coded_bytes += recs[q].bytes;
     }
     plan->wchunks.push_back(std::move(wc));
   }
@@ -1487,9 +1514,11 @@ int tk_wire_encode_device(const tk_wire_record* recs, int n_recs, const void* co
   std::vector<tk::WireUnit> units;
   tk::wire_layout(n.data(), d.data(), n_recs, &refs, &units);
   std::vector<tk::WireSegDev> segs;
-  for (const tk::WireSegRef& r : refs)
-    segs.push_back({(const int32_t*)src[r.rec] + r.e0, recs[r.rec].diff ? (const int32_t*)src[r.rec - 1] + r.e0 : nullptr,
-                    r.n, 0});
+  for (const tk::WireSegRef& r : refs) {
+    const int64_t e0 = tk::wire_elem_bytes(recs[r.rec].kind) * r.e0;
+    segs.push_back({(const char*)src[r.rec] + e0, recs[r.rec].diff ? (const char*)src[r.rec - 1] + e0 : nullptr, r.n,
+                    recs[r.rec].kind});
+  }
   hipStream_t s = tk::as_stream(stream);
   void* dev = nullptr;
   TK_HIP(hipMalloc(&dev, segs.size() * sizeof(tk::WireSegDev) + 64));

@@ -1,5 +1,5 @@
 // Host side of the trace wire format (tk_wire.h): the decoder that widens a wire buffer into the
-// trace image on a fixed thread pool, and a reference encoder so the decoder is testable without
+// trace image (and rebuilds clamp-predicted 1-byte records from the image bytes before them) on a fixed thread pool, and a reference encoder so the decoder is testable without
 // a device.  Plain C++ (no HIP): also compiled alone into the sanitizer check of tools/wire_check.cc.
 #include "tk_wire.h"
 
@@ -148,6 +148,24 @@ void widen_w(int w, char* dst, const char* prev, const uint8_t* p, int cnt, uint
   }
 }
 
+// 1-byte blocks: dst = clamp(prev, lo, hi) in the record's dtype, 32 bytes at a time.  int8 is
+// compared as uint8 with the sign bit flipped (`flip` 0x80; lo and hi come flipped already), so
+// both dtypes are one unsigned byte min / max, which the compiler keeps in vector registers.
+inline uint8_t clamp_u8(uint8_t x, uint8_t lo, uint8_t hi) {
+  x = x < lo ? lo : x;
+  return x > hi ? hi : x;
+}
+void clamp_block(char* dst, const char* prev, int cnt, uint8_t lo, uint8_t hi, uint8_t flip) {
+  int i = 0;
+  for (; i + 32 <= cnt; i += 32) {
+    uint8_t v[32];
+    std::memcpy(v, prev + i, 32);
+    for (int j = 0; j < 32; ++j) v[j] = (uint8_t)(clamp_u8((uint8_t)(v[j] ^ flip), lo, hi) ^ flip);
+    std::memcpy(dst + i, v, 32);
+  }
+  for (; i < cnt; ++i) dst[i] = (char)(clamp_u8((uint8_t)((uint8_t)prev[i] ^ flip), lo, hi) ^ flip);
+}
+
 // Decodes segment i; returns its length rounded to 64 B, or -1 if it does not lie inside the
 // payload (nothing past the payload is read, nothing outside the segment's record is written).
 int64_t decode_seg(const WireJob& j, int64_t i, const char* payload, int64_t payload_bytes) {
@@ -161,12 +179,25 @@ int64_t decode_seg(const WireJob& j, int64_t i, const char* payload, int64_t pay
   const char* p = payload + off;
   const uint8_t* widths = (const uint8_t*)p + wire_align(4 * (int64_t)nb, 16);
   int64_t len = hdr;
+  const int max_w = sg.kind == kWireI32 ? 4 : 1;
   for (int b = 0; b < nb; ++b) {
-    if (widths[b] > 4) return -1;
+    if (widths[b] > max_w) return -1;
     len += (int64_t)widths[b] * std::min(kWireBlock, sg.n - b * kWireBlock);
   }
   if (len > payload_bytes - off) return -1;
   const uint8_t* q = (const uint8_t*)p + hdr;
+  if (sg.kind != kWireI32) {
+    const uint8_t flip = sg.kind == kWireI8 ? 0x80 : 0;
+    for (int b = 0; b < nb; ++b) {
+      const int cnt = std::min(kWireBlock, sg.n - b * kWireBlock);
+      char* dst = sg.dst + (int64_t)b * kWireBlock;
+      const uint8_t lo = (uint8_t)p[4 * b], hi = (uint8_t)p[4 * b + 1];
+      if (widths[b]) std::memcpy(dst, q, (size_t)cnt), q += cnt;
+      else if (sg.prev) clamp_block(dst, sg.prev + (int64_t)b * kWireBlock, cnt, lo ^ flip, hi ^ flip, flip);
+      else std::memset(dst, lo, (size_t)cnt);
+    }
+    return wire_align(len, 64);
+  }
   for (int b = 0; b < nb; ++b) {
     const int cnt = std::min(kWireBlock, sg.n - b * kWireBlock);
     const int w = widths[b];
@@ -245,6 +276,32 @@ int64_t encode_seg(const char* src, const char* prev, int n, char* out) {
   return (char*)q - out;
 }
 
+// one segment of a 1-byte record (clamp-predicted from `prev` unless it is null)
+int64_t encode_seg8(const char* src, const char* prev, int n, int kind, char* out) {
+  const int nb = (n + kWireBlock - 1) / kWireBlock;
+  const int64_t hdr = wire_header_bytes(nb);
+  std::memset(out, 0, (size_t)hdr);
+  uint8_t* widths = (uint8_t*)out + wire_align(4 * (int64_t)nb, 16);
+  uint8_t* q = (uint8_t*)out + hdr;
+  const uint8_t flip = kind == kWireI8 ? 0x80 : 0;
+  for (int b = 0; b < nb; ++b) {
+    const int cnt = std::min(kWireBlock, n - b * kWireBlock);
+    const uint8_t* a = (const uint8_t*)src + (int64_t)b * kWireBlock;
+    uint8_t lo = 0xFF, hi = 0;  // in the flipped (unsigned) order
+    for (int i = 0; i < cnt; ++i) lo = std::min<uint8_t>(lo, a[i] ^ flip), hi = std::max<uint8_t>(hi, a[i] ^ flip);
+    bool coded = lo == hi;
+    if (prev && !coded) {
+      const uint8_t* pv = (const uint8_t*)prev + (int64_t)b * kWireBlock;
+      coded = true;
+      for (int i = 0; i < cnt && coded; ++i) coded = clamp_u8((uint8_t)(pv[i] ^ flip), lo, hi) == (uint8_t)(a[i] ^ flip);
+    }
+    out[4 * b] = (char)(lo ^ flip), out[4 * b + 1] = (char)(hi ^ flip);
+    widths[b] = coded ? 0 : 1;
+    if (!coded) std::memcpy(q, a, (size_t)cnt), q += cnt;
+  }
+  return (char*)q - out;
+}
+
 struct HostPlan {
   std::vector<WireSegRef> segs;
   std::vector<WireUnit> units;
@@ -260,17 +317,21 @@ int host_plan(const tk_wire_record* recs, int n_recs, int64_t image_bytes, HostP
   for (int i = 0; i < n_recs; ++i) {
     n[i] = recs[i].n_elems;
     d[i] = recs[i].diff != 0;
-    const bool inside = recs[i].offset >= 0 && recs[i].n_elems >= 1 && recs[i].n_elems <= ((int64_t)1 << 40) &&
-                        (image_bytes < 0 || (recs[i].offset <= image_bytes && 4 * recs[i].n_elems <= image_bytes - recs[i].offset));
-    if (!inside || (d[i] && (i == 0 || recs[i - 1].n_elems != recs[i].n_elems))) {
+    const int kind = recs[i].kind;
+    const int64_t esize = wire_elem_bytes(kind);
+    const bool inside = kind >= kWireI32 && kind <= kWireU8 && recs[i].offset >= 0 && recs[i].n_elems >= 1 &&
+                        recs[i].n_elems <= ((int64_t)1 << 40) &&
+                        (image_bytes < 0 ||
+                         (recs[i].offset <= image_bytes && esize * recs[i].n_elems <= image_bytes - recs[i].offset));
+    if (!inside || (d[i] && (i == 0 || recs[i - 1].n_elems != recs[i].n_elems || recs[i - 1].kind != kind))) {
       set_error(std::string(who) + ": record " + std::to_string(i) +
-                " lies outside the image or is differenced against a record of another size");
+                " is of no known kind, lies outside the image or follows (diff) a record of another size or kind");
       return TK_ERR_INVALID_ARG;
     }
   }
   wire_layout(n.data(), d.data(), n_recs, &p->segs, &p->units);
   p->bound = wire_table_bytes((int64_t)p->segs.size());
-  for (const WireSegRef& s : p->segs) p->bound += wire_seg_bound(s.n);
+  for (const WireSegRef& s : p->segs) p->bound += wire_seg_bound(s.n, wire_elem_bytes(recs[s.rec].kind));
   return TK_OK;
 }
 }  // namespace
@@ -299,11 +360,14 @@ int64_t tk_wire_encode_host(const tk_wire_record* recs, int n_recs, const void* 
   int64_t cursor = 0;
   for (size_t i = 0; i < p.segs.size(); ++i) {
     const tk::WireSegRef& s = p.segs[i];
-    const char* src = (const char*)image + recs[s.rec].offset + 4 * s.e0;
-    const char* prev = recs[s.rec].diff ? (const char*)image + recs[s.rec - 1].offset + 4 * s.e0 : nullptr;
+    const int kind = recs[s.rec].kind;
+    const int64_t e0 = tk::wire_elem_bytes(kind) * s.e0;
+    const char* src = (const char*)image + recs[s.rec].offset + e0;
+    const char* prev = recs[s.rec].diff ? (const char*)image + recs[s.rec - 1].offset + e0 : nullptr;
     const uint32_t start = (uint32_t)(cursor / 64);
     std::memcpy((char*)wire + 4 * i, &start, 4);
-    const int64_t len = tk::encode_seg(src, prev, s.n, payload + cursor);
+    const int64_t len = kind == tk::kWireI32 ? tk::encode_seg(src, prev, s.n, payload + cursor)
+                                             : tk::encode_seg8(src, prev, s.n, kind, payload + cursor);
     const int64_t padded = tk::wire_align(len, 64);
     std::memset(payload + cursor + len, 0, (size_t)(padded - len));
     cursor += padded;
@@ -323,9 +387,11 @@ int tk_wire_decode(const tk_wire_record* recs, int n_recs, const void* wire, int
   std::vector<tk::WireSegHost> segs(p.segs.size());
   for (size_t i = 0; i < p.segs.size(); ++i) {
     const tk::WireSegRef& s = p.segs[i];
-    segs[i].dst = (char*)image + recs[s.rec].offset + 4 * s.e0;
-    segs[i].prev = recs[s.rec].diff ? (const char*)image + recs[s.rec - 1].offset + 4 * s.e0 : nullptr;
+    const int64_t e0 = tk::wire_elem_bytes(recs[s.rec].kind) * s.e0;
+    segs[i].dst = (char*)image + recs[s.rec].offset + e0;
+    segs[i].prev = recs[s.rec].diff ? (const char*)image + recs[s.rec - 1].offset + e0 : nullptr;
     segs[i].n = s.n;
+    segs[i].kind = recs[s.rec].kind;
   }
   tk::WireJob job;
   job.wire = (const char*)wire;

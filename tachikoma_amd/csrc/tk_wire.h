@@ -1,6 +1,7 @@
 // Trace wire format: int32 trace records leave the device losslessly narrowed and are widened
-// on the host (tk_wire.cc: host decoder, thread pool and reference encoder; tk_elementwise.hip:
-// the device encoder; tk_runtime.cc: the packed capture that uses them).
+// on the host; 1-byte records that are a clamp of the record before them leave as that statement
+// and are rebuilt on the host (tk_wire.cc: host decoder, thread pool and reference encoder;
+// tk_elementwise.hip: the device encoder; tk_runtime.cc: the packed capture that uses them).
 //
 // A record of n int32 elements is cut into blocks of kWireBlock elements and segments of
 // kWireSegBlocks blocks (the last block / segment of a record may be short).  The coded value of
@@ -17,6 +18,16 @@
 // Block payload of cnt elements: `width` byte planes of cnt bytes, plane k holding byte k of every
 // offset (a full block's planes are 256 B, so the device writes them with 16-byte stores and the
 // host widens them with byte-to-dword vector loops).
+//
+// 1-byte records (kind int8 / uint8) keep this geometry with one element per byte and two block
+// forms each.  A plain record: width 0 is a constant block (the value in byte 0 of the base),
+// width 1 one raw plane of the record's own bytes.  A clamp-predicted record (its predecessor is a
+// record of the same kind and element count): width 0 means block == clamp(predecessor's block, lo,
+// hi), with lo / hi the block's own minimum / maximum compared in the record's dtype and stored in
+// base bytes 0 / 1; width 1 is the raw plane (not a residual), the escape of a block the clamp does
+// not reproduce.  If rec == clamp(prev, L, H) holds on a block for any L, H then
+// clamp(prev, min(rec), max(rec)) reproduces it, so the prediction needs no clip attributes and
+// any data round-trips.  Other widths are refused in a 1-byte segment.
 #pragma once
 
 #include <stdint.h>
@@ -32,23 +43,27 @@ constexpr int kWireSegElems = kWireBlock * kWireSegBlocks;
 inline int64_t wire_align(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 inline int64_t wire_table_bytes(int64_t n_seg) { return wire_align(4 * n_seg, 64); }
 inline int64_t wire_header_bytes(int nb) { return wire_align(4 * (int64_t)nb, 16) + wire_align(nb, 16); }
-// worst case (every block raw) of a segment of n elements
-inline int64_t wire_seg_bound(int n) {
-  return wire_align(wire_header_bytes((n + kWireBlock - 1) / kWireBlock) + 4 * (int64_t)n, 64);
+// element kind of a record / segment (tk_wire_record.kind)
+enum WireKind : int32_t { kWireI32 = 0, kWireI8 = 1, kWireU8 = 2 };
+inline int wire_elem_bytes(int kind) { return kind == kWireI32 ? 4 : 1; }
+// worst case (every block raw) of a segment of n elements of esize bytes
+inline int64_t wire_seg_bound(int n, int esize = 4) {
+  return wire_align(wire_header_bytes((n + kWireBlock - 1) / kWireBlock) + esize * (int64_t)n, 64);
 }
 
 // device encoder's view of a segment
 struct WireSegDev {
-  const int32_t* src;
-  const int32_t* prev;  // differenced against (device), or null
+  const void* src;
+  const void* prev;  // differenced against / clamp-predicted from (device), or null
   int32_t n;
-  int32_t pad;
+  int32_t kind;
 };
 // host decoder's view: destinations in the trace image, any alignment
 struct WireSegHost {
   char* dst;
-  const char* prev;  // differenced against (already decoded image bytes), or null
+  const char* prev;  // differenced against / clamp-predicted from (image bytes already present), or null
   int32_t n;
+  int32_t kind;
 };
 // One decoder work item: segments first, first + stride, ... (`count` of them), decoded in this
 // order by one thread: the same segment of a chain of records differenced against each other.
@@ -61,8 +76,9 @@ struct WireSegRef {
   int64_t e0;  // first element
 };
 
-// Segments and decode units of a run of records (diff[i]: record i is differenced against
-// record i - 1, which then has the same element count).
+// Segments and decode units of a run of records (diff[i]: record i is decoded after the same
+// segment of record i - 1, which then has the same element count: differenced against it, or
+// clamp-predicted from it).  Segments count elements, whatever their size.
 void wire_layout(const int64_t* n_elems, const int32_t* diff, int n_recs, std::vector<WireSegRef>* segs,
                  std::vector<WireUnit>* units);
 

@@ -699,6 +699,11 @@ def exec_groups(plan: Plan, fuse: bool = True) -> List[ExecGroup]:
         if len(cs) != 1 or cs[0].op != "qnn.add" or cs[0].name in taken:
             return None
         add = cs[0]
+        # only the MFMA conv kernels have the fused join (csrc/tk_gemm.hip, use_mfma_conv: one group,
+        # at least 16 output and 3 input channels); a smaller conv keeps its block and the add its own
+        w_shape = plan.tensor(chain[0].inputs[1]).shape
+        if chain[0].attrs.get("groups", 1) != 1 or w_shape[0] < 16 or w_shape[1] < 3:
+            return None
         if add.out.dtype != rq.out.dtype or add.inputs[0] == add.inputs[1] or not add.attrs.get("per_tensor") \
                 or add.attrs.get("compute_dtype", "int64") != "int64":
             return None

@@ -1015,7 +1015,9 @@ class DeviceModule:
 
     def set_trace_wire(self, enable: bool) -> None:
         """Trace wire of the packed capture: int32 records cross the link narrowed and are widened
-        on the host (tk_module_set_trace_wire; on by default, TK_TRACE_WIRE=0 forces it off)."""
+        on the host, clip records cross as clamps of the record before them and are rebuilt there
+        (tk_module_set_trace_wire; on by default, TK_TRACE_WIRE=0 forces it off, TK_WIRE_CLAMP=0
+        at module creation keeps the clip records raw)."""
         _lib.check(self.lib.tk_module_set_trace_wire(self.handle, int(enable)), "tk_module_set_trace_wire")
 
     def wire_stats(self) -> List[dict]:

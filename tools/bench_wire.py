@@ -3,7 +3,8 @@
 of `--model` at `--batch` samples, with the trace wire on and off in one process,
 
   * ms per step of K back-to-back traced steps (as bench.py queues them),
-  * wire bytes per step against the raw trace bytes, and the coded (int32) share,
+  * wire bytes per step against the raw trace bytes, and the coded share (int32 records and the
+    clip records coded as clamps; TK_WIRE_CLAMP=0 in the environment keeps the latter raw),
   * the wire stream's rate: bytes over the sum of the chunks' wire-work intervals
     (tk_module_copy_trace's events) -- with wire off that is the plain chunk copy rate, the
     in-run pinned-copy probe to set it against,

@@ -1,5 +1,5 @@
 // Stand-alone check of the host wire codec (csrc/tk_wire.cc) for sanitizer builds: the cases of
-// tests/test_wire_codec.py restated in C++ with heap buffers of exactly the sizes the codec may
+// tests/test_wire_codec.py and tests/test_wire_codec8.py restated in C++ with heap buffers of exactly the sizes the codec may
 // touch, so that AddressSanitizer sees any byte read past a wire buffer or written outside a
 // record, and UBSan any overflowing or misaligned access.  CPU only; never needs a device.
 //
@@ -85,7 +85,136 @@ static int roundtrip(const Case& c, int threads, int corrupt = 0) {
   return rc;
 }
 
+// The same for records of any kind (kind 0: `data` holds int32 elements as bytes).  `corrupt`:
+// 1 truncated payload, 5 the first segment's first block states width 2.  *wire_bytes: the size.
+struct AnyRec {
+  std::vector<uint8_t> data;
+  int kind, diff;
+};
+static int roundtrip_any(const std::vector<AnyRec>& c, int threads, int corrupt = 0, int64_t* wire_bytes = nullptr) {
+  const int n = (int)c.size();
+  std::vector<tk_wire_record> r(n);
+  int64_t at = 3;
+  for (int i = 0; i < n; ++i) {
+    const int64_t esize = c[i].kind ? 1 : 4;
+    r[i] = {at, (int64_t)c[i].data.size() / esize, c[i].diff, c[i].kind};
+    at += (int64_t)c[i].data.size() + 5;
+  }
+  const int64_t total = at;
+  std::unique_ptr<uint8_t[]> src(new uint8_t[total]), out(new uint8_t[total]);
+  std::memset(src.get(), 0xA5, total);
+  for (int i = 0; i < n; ++i) std::memcpy(src.get() + r[i].offset, c[i].data.data(), c[i].data.size());
+  std::memcpy(out.get(), src.get(), total);
+  for (int i = 0; i < n; ++i) std::memset(out.get() + r[i].offset, 0x3C, c[i].data.size());
+  const int64_t bound = tk_wire_bound(r.data(), n);
+  CHECK(bound > 0);
+  if (bound <= 0) return (int)bound;
+  std::unique_ptr<uint8_t[]> big(new uint8_t[bound]);
+  int64_t nb = tk_wire_encode_host(r.data(), n, src.get(), total, big.get(), bound);
+  CHECK(nb > 0 && nb <= bound);
+  if (wire_bytes) *wire_bytes = nb;
+  if (corrupt == 1) nb -= 64;
+  std::unique_ptr<uint8_t[]> wire(new uint8_t[nb > 0 ? nb : 1]);
+  std::memcpy(wire.get(), big.get(), nb);
+  if (corrupt == 5) {  // table of <= 16 segments: 64 B
+    const size_t nb0 = std::min<size_t>(64, (c[0].data.size() / (c[0].kind ? 1 : 4) + 255) / 256);
+    wire[64 + ((4 * nb0 + 15) & ~(size_t)15)] = 2;
+  }
+  const int rc = tk_wire_decode(r.data(), n, wire.get(), nb, out.get(), total, threads);
+  if (!corrupt) CHECK(rc == 0 && std::memcmp(out.get(), src.get(), total) == 0);
+  return rc;
+}
+
+static std::vector<uint8_t> random_bytes(int n, int lo, int hi) {  // values in [lo, hi] as int, stored as bytes
+  std::vector<uint8_t> v(n);
+  for (int i = 0; i < n; ++i) v[i] = (uint8_t)(lo + (int)(g_rng() % (uint64_t)(hi - lo + 1)));
+  return v;
+}
+static std::vector<uint8_t> clamped(const std::vector<uint8_t>& p, int kind, int lo, int hi) {
+  std::vector<uint8_t> v(p.size());
+  for (size_t i = 0; i < p.size(); ++i) {
+    const int x = kind == 1 ? (int)(int8_t)p[i] : (int)p[i];
+    v[i] = (uint8_t)std::min(std::max(x, lo), hi);
+  }
+  return v;
+}
+
+// 1-byte records: plain (constant, random) and clamp-predicted pairs of both kinds, a pair with one
+// element off by one in the last, short block (only that block goes raw), an int32 chain and a
+// clamp pair in one buffer, and the refusals.
+static void byte_cases(int n) {
+  auto size_of = [&](int raw_blocks_bytes, int n_recs) {  // records of one segment each (n <= 16384)
+    const int64_t nbk = (n + 255) / 256, hdr = ((4 * nbk + 15) & ~15) + ((nbk + 15) & ~15);
+    return 64 + (n_recs - 1) * ((hdr + 63) & ~(int64_t)63) + ((hdr + raw_blocks_bytes + 63) & ~(int64_t)63);
+  };
+  for (int kind : {1, 2}) {
+    const int lo_t = kind == 1 ? -128 : 0, hi_t = kind == 1 ? 127 : 255;
+    const std::vector<uint8_t> prev = random_bytes(n, lo_t, hi_t);
+    std::vector<std::vector<uint8_t>> recs;
+    recs.push_back(clamped(prev, kind, lo_t + 128, hi_t));       // relu: only the lower bound is hit
+    recs.push_back(clamped(prev, kind, lo_t + 60, hi_t - 70));   // both bounds (uint8: values above 127 on both sides)
+    recs.push_back(prev);                                        // identity
+    recs.push_back(clamped(prev, kind, lo_t, hi_t));             // bounds at the dtype's ends
+    for (const auto& rec : recs)
+      for (int threads : {1, 0}) {
+        int64_t nb = 0;
+        roundtrip_any({{prev, kind, 0}, {rec, kind, 1}}, threads, 0, &nb);
+        if (n <= 16384 && n >= 256) CHECK(nb > (int64_t)n && nb < 2 * (int64_t)n);  // prev raw, rec predicted
+      }
+    {  // one element off by one, last in the final block: only that block is raw
+      std::vector<uint8_t> rec = clamped(prev, kind, lo_t + 60, hi_t - 70);
+      std::vector<uint8_t> c0(n, (uint8_t)7);
+      rec[n - 1] = (uint8_t)(rec[n - 1] == (uint8_t)(lo_t + 60) ? rec[n - 1] + 1 : rec[n - 1] - 1);
+      int64_t nb = 0;
+      roundtrip_any({{c0, kind, 0}, {rec, kind, 1}}, 0, 0, &nb);
+      // the constant predecessor cannot predict a block of two values, so compare against prev too
+      roundtrip_any({{prev, kind, 0}, {rec, kind, 1}}, 0, 0, &nb);
+      if (n <= 16384) {
+        const int last = n - (n - 1) / 256 * 256;
+        int64_t raw_prev = 0;
+        for (int b = 0; b < n; b += 256) {
+          const int cnt = std::min(256, n - b);
+          if (!std::all_of(prev.begin() + b, prev.begin() + b + cnt, [&](uint8_t x) { return x == prev[b]; })) raw_prev += cnt;
+        }
+        const int64_t nbk = (n + 255) / 256, hdr = ((4 * nbk + 15) & ~15) + ((nbk + 15) & ~15);
+        const bool last_const = last == 1;  // a one-element block is constant: width 0
+        CHECK(nb == 64 + ((hdr + raw_prev + 63) & ~(int64_t)63) + ((hdr + (last_const ? 0 : last) + 63) & ~(int64_t)63));
+      }
+    }
+    {  // plain records: constant (header only) and random (every block raw)
+      int64_t nb = 0;
+      roundtrip_any({{std::vector<uint8_t>(n, (uint8_t)0x91), kind, 0}}, 0, 0, &nb);
+      if (n <= 16384) CHECK(nb == size_of(0, 1));
+      roundtrip_any({{prev, kind, 0}}, 1);
+    }
+    {  // an int32 chain and a clamp pair in one buffer
+      Rec a = span(n, -60000, 120000), b(n);
+      for (int i = 0; i < n; ++i) b[i] = a[i] + i / 7 * 3 - 11;
+      auto raw = [](const Rec& v) {
+        std::vector<uint8_t> o(4 * v.size());
+        std::memcpy(o.data(), v.data(), o.size());
+        return o;
+      };
+      const std::vector<AnyRec> mix = {{raw(a), 0, 0}, {raw(b), 0, 1}, {prev, kind, 0}, {recs[1], kind, 1}};
+      for (int threads : {1, 0}) roundtrip_any(mix, threads);
+      CHECK(roundtrip_any(mix, 0, 1) == TK_ERR_INVALID_ARG);
+    }
+    CHECK(roundtrip_any({{prev, kind, 0}, {recs[1], kind, 1}}, 0, 5) == TK_ERR_INVALID_ARG);
+    CHECK(roundtrip_any({{prev, kind, 0}, {recs[1], kind, 1}}, 0, 1) == TK_ERR_INVALID_ARG);
+    // a clamp record whose predecessor has another size or kind
+    tk_wire_record bad[2] = {{3, n, 0, kind}, {3 + n + 5, n, 1, 3 - kind}};
+    CHECK(tk_wire_bound(bad, 2) == TK_ERR_INVALID_ARG);
+    bad[1].kind = kind, bad[0].n_elems = n + 1;
+    CHECK(tk_wire_bound(bad, 2) == TK_ERR_INVALID_ARG);
+    bad[0].n_elems = n, bad[0].kind = 0;
+    CHECK(tk_wire_bound(bad, 2) == TK_ERR_INVALID_ARG);
+    bad[0].kind = 7, bad[1].diff = 0;
+    CHECK(tk_wire_bound(bad, 2) == TK_ERR_INVALID_ARG);
+  }
+}
+
 int main() {
+  for (int n : {1, 15, 16, 17, 255, 256, 257, 3 * 256 + 17, 2 * 16384 + 300}) byte_cases(n);
   const int sizes[] = {1, 255, 256, 257, 3 * 256 + 17, 2 * 16384 + 300};
   for (int n : sizes) {
     std::vector<Case> cases;
