@@ -704,7 +704,20 @@ int tk_module_wire_stats(tk_module* mod, double* out, int max_chunks);
  * table or segment that does not lie inside wire_bytes is refused with TK_ERR_INVALID_ARG and
  * nothing outside `wire` is read.  tk_wire_encode_device: the device encoder on device buffers
  * src[i] (one per record), writing into `wire` (device-accessible, tk_wire_bound bytes, 64-byte
- * aligned); synchronises `stream`. */
+ * aligned); synchronises `stream`.
+ *
+ * tk_wire_pack_device: the deterministic device encoder behind packed trace files (below).  Same
+ * records and sources as tk_wire_encode_device; `wire` is device-accessible (normally HBM), 64-byte
+ * aligned and holds at least tk_wire_bound bytes (a smaller wire_cap is refused before any launch).
+ * Synchronises `stream` and returns the bytes used (table plus segments) or a negative tk_status.
+ * Bytes [0, used) are byte for byte what tk_wire_encode_host writes for the same records: segment i
+ * starts where the host encoder puts it, and the table padding, the header padding and each
+ * segment's tail up to 64 B are zero, so equal records give equal bytes on every run.  Three
+ * launches, none waiting on another workgroup: every segment's size, an exclusive prefix sum over
+ * the sizes (tiles of tk_wire_pack_tile() entries, as many levels as the segment count needs), and
+ * the encoder's stores at the starts the sum gives.  A total that does not fit the table's u32
+ * units is refused with TK_ERR_UNSUPPORTED.  Calls are serialised on a device scratch that is kept
+ * between them. */
 typedef struct {
   int64_t offset;
   int64_t n_elems;
@@ -718,6 +731,9 @@ int tk_wire_decode(const tk_wire_record* recs, int n_recs, const void* wire, int
                    int64_t image_bytes, int threads);
 int tk_wire_encode_device(const tk_wire_record* recs, int n_recs, const void* const* src, void* wire,
                           int64_t wire_cap, void* stream);
+int64_t tk_wire_pack_device(const tk_wire_record* recs, int n_recs, const void* const* src, void* wire,
+                            int64_t wire_cap, void* stream);
+int tk_wire_pack_tile(void);
 int tk_wire_threads(void);
 
 /* Makes `stream` wait for the copies of the last traced run: call before writing any
@@ -774,9 +790,24 @@ int tk_ndlist_parse(const void* blob, int64_t blob_size, int cap, tk_array_meta*
                     int64_t* data_offsets, int64_t* shapes_storage, int shapes_cap, int* n_out);
 
 /* Trace container: "TKTRACE\0" | u64 version | u64 json_len | u64 params_off | u64 params_size |
- * u64 records_off | u64 records_size | json | pad | params blob | pad | records blob. */
+ * u64 records_off | u64 records_size | json | pad | params blob | pad | records blob.
+ *
+ * Version 2, the packed file (tachikoma_amd/trace_format.py: pack_trace / unpack_trace): header
+ * (version = 2), json and params blob as in version 1; the records section holds the wire coding:
+ *   u32 "TKPK" | u32 n_records | u64 plan_len | u64 wire_size | u64 raw_size | plan | pad to 8 |
+ *   wire (what tk_wire_encode_host / tk_wire_pack_device write for the coded records) | raw payloads
+ * with one plan entry per record, in trace order: u16 name_len, name, u8 dtype code, u8 bits,
+ * u8 ndim, u8 coding (tk_wire_record.kind, or 255 = raw), u8 diff, ndim x i64 shape, and for a raw
+ * record u64 offset, u64 size within the raw part.  The packers' planning rule looks at the record
+ * list alone: an int32 record is kind 0, differenced when the record before it is a coded int32
+ * record of the same shape; an int8 / uint8 record is kind 1 / 2, clamp-predicted when the record
+ * before it has the same kind and shape; every other dtype is raw.  Readers follow the stored plan
+ * and never recompute it.  tk_trace_layout / tk_trace_write_headers rebuild the version-1 layout
+ * and headers from the json, the params and the plan's names / dtypes / shapes, tk_wire_decode
+ * expands the coded records: unpacking gives the version-1 file byte for byte. */
 #define TK_TRACE_MAGIC 0x0045434152544B54ULL /* "TKTRACE\0" little-endian */
 #define TK_TRACE_VERSION 1
+#define TK_TRACE_VERSION_PACKED 2
 #define TK_TRACE_ALIGN 4096
 typedef struct {
   uint64_t magic, version, json_len, params_off, params_size, records_off, records_size;

@@ -424,6 +424,8 @@ SIGNATURES = {
     "tk_wire_decode": (ctypes.c_int, [ctypes.POINTER(tk_wire_record), ctypes.c_int, _VP, _I64, _VP, _I64, ctypes.c_int]),
     "tk_wire_encode_device": (ctypes.c_int, [ctypes.POINTER(tk_wire_record), ctypes.c_int, ctypes.POINTER(_VP), _VP,
                                              _I64, _VP]),
+    "tk_wire_pack_device": (_I64, [ctypes.POINTER(tk_wire_record), ctypes.c_int, ctypes.POINTER(_VP), _VP, _I64, _VP]),
+    "tk_wire_pack_tile": (ctypes.c_int, []),
     "tk_wire_threads": (ctypes.c_int, []),
     "tk_module_tune": (ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32),
                                       ctypes.POINTER(_F32)]),

@@ -109,6 +109,122 @@ class TraceCapture:
         return memoryview(self.image.numpy())
 
 
+class PackedCapture:
+    """One packed (version 2) trace file in the making: a device wire buffer, the pinned staging the
+    file is written from, and the device packer between them.
+
+    The records are packed where they lie (tk_wire_pack_device, which tells the host how many bytes
+    it used), the records the wire does not code are gathered behind the used prefix, and one copy
+    moves both into the staging at their place in the file.  No trace image exists and the host
+    decoder is not involved.  The staging is sized once from tk_wire_bound (head + worst-case wire +
+    raw records), not grown on demand: the worst case is the records' own size plus 2 %, and a
+    buffer that never moves can be written from while the other one fills."""
+
+    def __init__(self, module: DeviceModule, meta: Dict[str, Any]):
+        import ctypes
+        import torch
+        self.module = module
+        self.lib = module.lib
+        plan = module.plan
+        params = [(t.name, t.shape, t.dtype) for t in plan.params]
+        records = [(t.name, t.shape, t.dtype) for t in plan.records]
+        self.meta = dict(meta)
+        self.entries = tf.packed_entries(records)
+        # header, json and params blob are those of the version-1 file (laid out without records)
+        self.layout, self.records_off = tf.head_layout(tf.header_json(self.meta), params)
+        coded = [e for e in self.entries if e.coding != tf.RAW]
+        self.raw = [e for e in self.entries if e.coding == tf.RAW]
+        self.raw_bytes = sum(e.raw_size for e in self.raw)
+        self.recs, self.n_coded = tf._wire_records(self.entries, [0] * len(self.entries))
+        self.src = (ctypes.c_void_p * max(1, len(coded)))(*[module.buffers[e.name].data_ptr() for e in coded])
+        self.bound = 0
+        if self.n_coded:
+            self.bound = int(self.lib.tk_wire_bound(self.recs, self.n_coded))
+            if self.bound < 0:
+                _lib.check(self.bound, "tk_wire_bound")
+        self.section_head = len(tf.packed_section_head(self.entries, 0))
+        self.wire_off = self.records_off + self.section_head
+        self.wire = torch.empty(max(64, self.bound + self.raw_bytes), dtype=torch.uint8, device=module.device)
+        self.image = torch.empty(self.wire_off + self.bound + self.raw_bytes, dtype=torch.uint8, pin_memory=True)
+        self.ptr = self.image.data_ptr()
+        self.layout.write_headers(self.ptr, self.layout.total)
+        self.param_offsets = {p[0]: (off, p[1], p[2]) for p, off in zip(params, self.layout.param_offsets)}
+        self.refresh_params(list(self.param_offsets))
+        self.copy_stream = torch.cuda.Stream(device=module.device)
+        self.used = 0
+        self.size = 0
+        self.stats: Dict[str, float] = {}
+        self._copy_events = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+
+    def refresh_params(self, names) -> None:
+        """Copy the named params' device buffers into the params section (synchronous)."""
+        for name in names:
+            off, shape, dtype = self.param_offsets[name]
+            nbytes = int(np.prod(shape, dtype=np.int64)) * np.dtype(dtype).itemsize
+            self.image[off:off + nbytes].copy_(_as_bytes(self.module.buffers[name]))
+
+    def update_meta(self, **kw) -> None:
+        """As TraceCapture.update_meta: the json keeps the length it had when the capture was made."""
+        import torch
+        self.meta.update(kw)
+        text = tf.header_json(self.meta)
+        old = self.layout.json_text
+        if len(text.rstrip()) > len(old):
+            raise _lib.TachikomaError("trace header grew beyond its reserved slack")
+        text = text.rstrip().ljust(len(old))
+        self.layout.json_text = text
+        self.image[56:56 + len(text)].copy_(torch.frombuffer(bytearray(text.encode()), dtype=torch.uint8))
+
+    def pack(self, stream) -> int:
+        """Pack the records of the run queued on ``stream`` and start the copy into the staging;
+        returns the file's size.  Waits for the run (the packer reports its length to the host);
+        when it returns the record buffers may be overwritten by work queued on ``stream``."""
+        import ctypes
+        import struct
+        import torch
+        stream.synchronize()
+        t0 = time.perf_counter()
+        used = 0
+        if self.n_coded:
+            used = int(self.lib.tk_wire_pack_device(self.recs, self.n_coded, self.src,
+                                                    ctypes.c_void_p(self.wire.data_ptr()), self.bound,
+                                                    ctypes.c_void_p(_lib.stream_handle(stream))))
+            if used < 0:
+                _lib.check(used, "tk_wire_pack_device")
+        self.stats = {"pack_ms": (time.perf_counter() - t0) * 1e3}
+        with torch.cuda.stream(stream):
+            for e in self.raw:
+                self.wire[used + e.raw_off:used + e.raw_off + e.raw_size].copy_(
+                    _as_bytes(self.module.buffers[e.name]), non_blocking=True)
+        self.copy_stream.wait_stream(stream)
+        n = used + self.raw_bytes
+        with torch.cuda.stream(self.copy_stream):
+            self._copy_events[0].record(self.copy_stream)
+            if n:
+                self.image[self.wire_off:self.wire_off + n].copy_(self.wire[:n], non_blocking=True)
+            self._copy_events[1].record(self.copy_stream)
+        # the head's variable fields: version, records_size; the section (the copy lands behind it)
+        head = self.image.numpy()
+        section = tf.packed_section_head(self.entries, used)
+        head[8:16] = np.frombuffer(struct.pack("<Q", tf.PACKED_VERSION), np.uint8)
+        head[40:56] = np.frombuffer(struct.pack("<QQ", self.records_off, len(section) + n), np.uint8)
+        head[self.records_off:self.wire_off] = np.frombuffer(section, np.uint8)
+        self.used, self.size = used, self.wire_off + n
+        return self.size
+
+    def synchronize(self) -> None:
+        self.copy_stream.synchronize()
+        self.stats["copy_ms"] = self._copy_events[0].elapsed_time(self._copy_events[1])
+
+    def write(self, path: str) -> None:
+        t0 = time.perf_counter()
+        tf.write_file(path, self.ptr, self.size)
+        self.stats["write_ms"] = (time.perf_counter() - t0) * 1e3
+
+    def bytes(self) -> memoryview:
+        return memoryview(self.image.numpy())[:self.size]
+
+
 class BenchmarkResult:
     """Runtimes from benchmarking, in seconds (python/tvm/runtime/module.py:34-98): ``results``
     and their mean / std / median / min / max."""
@@ -181,6 +297,7 @@ class GraphModule:
         self.module = module
         self.plan = module.plan
         self._capture: Optional[TraceCapture] = None
+        self._packed: Optional[PackedCapture] = None
         self._meta = {"format": "tachikoma-trace", "version": tf.TRACE_VERSION, "model": "graph",
                       "target": "mi355x", "sample_offset": 0, "rank": 0, "world": 1,
                       "semantics": {"reference": "tvm llvm target without -mcpu", "requantize_compute_dtype":
@@ -200,6 +317,9 @@ class GraphModule:
         if self._capture is not None:
             self._capture.capture_stream.synchronize()
             self._capture = None
+        if self._packed is not None:
+            self._packed.copy_stream.synchronize()
+            self._packed = None
 
     def __enter__(self) -> "GraphModule":
         return self
@@ -295,8 +415,9 @@ class GraphModule:
                                           f"{a.dtype}{list(a.shape)} here")
             sel[name] = other.module.buffers[name]
         self.module.set_inputs(sel)
-        if self._capture is not None:
-            self._capture.refresh_params([n for n in sel if n in self._capture.param_offsets])
+        for cap in (self._capture, self._packed):
+            if cap is not None:
+                cap.refresh_params([n for n in sel if n in cap.param_offsets])
 
     _FUNCTIONS = ("set_input", "run", "get_output", "get_input", "get_num_outputs", "get_num_inputs",
                   "load_params", "share_params", "get_input_index", "get_input_info", "debug_get_output")
@@ -369,8 +490,9 @@ class GraphModule:
                                           f"the graph expects {t.dtype}{list(t.shape)}")
             sel[name] = arr
         self.module.set_inputs(sel)
-        if self._capture is not None:
-            self._capture.refresh_params([n for n in sel if n in self._capture.param_offsets])
+        for cap in (self._capture, self._packed):
+            if cap is not None:
+                cap.refresh_params([n for n in sel if n in cap.param_offsets])
 
     # -- trace / debug surface ---------------------------------------------
     def get_node_output(self, name: str) -> NDArrayView:
@@ -384,17 +506,38 @@ class GraphModule:
             self._capture = TraceCapture(self.module, self._meta)
         return self._capture
 
+    def packed_capture(self) -> PackedCapture:
+        if self._packed is None:
+            self._packed = PackedCapture(self.module, self._meta)
+        return self._packed
+
     def set_trace_meta(self, **kw) -> None:
         self._meta.update(kw)
-        if self._capture is not None:
-            self._capture.update_meta(**kw)
+        for cap in (self._capture, self._packed):
+            if cap is not None:
+                cap.update_meta(**kw)
 
-    def dump_trace(self, path: str, sample_offset: Optional[int] = None) -> str:
-        """Write the trace of the last run (re-runs with capture if the last run was not traced)."""
+    def dump_trace(self, path: str, sample_offset: Optional[int] = None, packed: bool = False) -> str:
+        """Write the trace of the last run (re-runs with capture if the last run was not traced).
+
+        With ``packed`` the file is a packed (version 2) trace: the run is compute-only, the records
+        are packed on the device (tk_wire_pack_device) and one copy moves the used prefix of the wire
+        buffer and the records the wire does not code into pinned staging, which is written out; no
+        trace image is captured and the host decoder is not used.  The staging is sized from
+        tk_wire_bound when the first packed trace is dumped (PackedCapture), not grown on demand.
+        trace_format.unpack_trace gives back exactly the file ``packed=False`` writes, and
+        trace_format.pack_trace of that file gives exactly this one."""
         import torch
         if sample_offset is not None:
             self.set_trace_meta(sample_offset=int(sample_offset))
         stream = torch.cuda.current_stream(self.module.device)
+        if packed:
+            cap = self.packed_capture()
+            self.module.run(stream)
+            cap.pack(stream)
+            cap.synchronize()
+            cap.write(path)
+            return path
         cap = self.trace_capture()
         cap.capture_inputs(stream)
         self.module.run(stream, cap.capture_stream, cap.host_dst)

@@ -715,6 +715,14 @@ int pack_records_impl(const void* table, int nrec, int64_t blocks, void* mirror,
 // the raw plane, which is the lane's 16 loaded bytes stored as they are.
 __device__ __forceinline__ uint32_t wire_byte(const uint32_t* w, int j) { return (w[j >> 2] >> (8 * (j & 3))) & 0xFFu; }
 
+// The packer of trace files (tk_wire_pack_device) runs the same code twice around a prefix sum, so
+// that segment i lies where the host encoder puts it whatever order the workgroups finish in:
+// kWireSize stops once the widths are known and writes the segment's size in 64-byte units to
+// table[i]; kWirePlace reads the segment's start from table[i] (the scanned sizes) instead of taking
+// it from the cursor and also zeroes the segment's tail up to 64 B.  kWireCursor is the live wire.
+enum { kWireCursor = 0, kWireSize = 1, kWirePlace = 2 };
+
+template <int kMode>
 __global__ __launch_bounds__(256) void wire_encode_kernel(const WireSegDev* __restrict__ segs, uint32_t* cursor,
                                                           uint32_t* __restrict__ table, uint8_t* __restrict__ payload,
                                                           uint32_t cap_units) {
@@ -840,10 +848,15 @@ __global__ __launch_bounds__(256) void wire_encode_kernel(const WireSegDev* __re
       off += s_w[b] * (uint32_t)min(kWireBlock, n - b * kWireBlock);
     }
     const uint32_t units = (off + 63) >> 6;
-    const uint32_t start = atomicAdd(cursor, units);
-    table[blockIdx.x] = start;
+    if constexpr (kMode == kWireSize) {
+      table[blockIdx.x] = units;
+      return;
+    }
+    const uint32_t start = kMode == kWirePlace ? table[blockIdx.x] : atomicAdd(cursor, units);
+    if constexpr (kMode == kWireCursor) table[blockIdx.x] = start;
     s_start = start <= cap_units && units <= cap_units - start ? start : 0xFFFFFFFFu;
   }
+  if constexpr (kMode == kWireSize) return;
   __syncthreads();
   if (s_start == 0xFFFFFFFFu) return;
   uint8_t* out = payload + (uint64_t)s_start * 64;
@@ -895,6 +908,12 @@ __global__ __launch_bounds__(256) void wire_encode_kernel(const WireSegDev* __re
       }
     }
   }
+  if constexpr (kMode == kWirePlace) {
+    // the tail: fewer than 64 bytes, none of them a plane's
+    const uint32_t end = s_off[nb - 1] + s_w[nb - 1] * (uint32_t)(n - (nb - 1) * kWireBlock);
+    const uint32_t at = end + threadIdx.x;
+    if (at < ((end + 63) & ~63u)) out[at] = 0;
+  }
 }
 
 int wire_encode_impl(const WireSegDev* segs, int64_t n_seg, uint32_t* cursor, void* wire, int64_t wire_bytes,
@@ -903,8 +922,122 @@ int wire_encode_impl(const WireSegDev* segs, int64_t n_seg, uint32_t* cursor, vo
   TK_CHECK_ARG(segs && cursor && wire && n_seg > 0 && n_seg < ((int64_t)1 << 31) && ((uintptr_t)wire & 63) == 0 &&
                wire_bytes >= table, "bad arguments");
   const int64_t cap_units = std::min<int64_t>((wire_bytes - table) / 64, 0xFFFFFFF0ll);
-  hipLaunchKernelGGL(wire_encode_kernel, dim3((unsigned)n_seg), dim3(256), 0, s, segs, cursor, (uint32_t*)wire,
+  hipLaunchKernelGGL(wire_encode_kernel<kWireCursor>, dim3((unsigned)n_seg), dim3(256), 0, s, segs, cursor, (uint32_t*)wire,
                      (uint8_t*)wire + table, (uint32_t)cap_units);
+  TK_LAUNCH_CHECK();
+  return TK_OK;
+}
+
+// ---------------------------------------------------------------- trace file packer
+// tk_wire_pack_device: the wire format with segment i where the host encoder puts it, so that the
+// same records give the same bytes on every run and the length is known before the copy.  Three
+// steps, none of which waits for another workgroup: the size pass leaves every segment's size (64-byte
+// units) in the table, an exclusive prefix sum turns the table into the starts, the place pass
+// stores the segments there.
+//
+// The prefix sum works on tiles of kWireScanTile entries, one workgroup each, eight consecutive
+// entries to a thread: a tile is scanned on its own (in place) and its total goes to the next level,
+// which is scanned the same way until a level is a single tile; then each level's offsets are added
+// to the tiles of the level below, top down.  A segment is at most 1030 units, so a tile's own sums
+// fit 32 bits; the levels above and the grand total are 64-bit, and the caller refuses a total that
+// does not fit the table's u32 before anything is placed.
+constexpr int kWireScanItems = kWireScanTile / 256;
+
+// v[i] <- v[tile start] + ... + v[i - 1] within each tile of n entries; sums[tile] <- the tile's total
+template <typename T>
+__global__ __launch_bounds__(256) void wire_scan_tile_kernel(T* v, uint64_t* __restrict__ sums, int64_t n) {
+  __shared__ uint64_t s_sum[256];
+  const int t = threadIdx.x;
+  const int64_t i0 = (int64_t)blockIdx.x * kWireScanTile + (int64_t)t * kWireScanItems;
+  T x[kWireScanItems];
+  uint64_t mine = 0;
+#pragma unroll
+  for (int j = 0; j < kWireScanItems; ++j) {
+    x[j] = i0 + j < n ? v[i0 + j] : (T)0;
+    mine += x[j];
+  }
+  s_sum[t] = mine;
+  __syncthreads();
+  for (int d = 1; d < 256; d <<= 1) {
+    const uint64_t below = t >= d ? s_sum[t - d] : 0;
+    __syncthreads();
+    s_sum[t] += below;
+    __syncthreads();
+  }
+  uint64_t at = s_sum[t] - mine;
+#pragma unroll
+  for (int j = 0; j < kWireScanItems; ++j) {
+    if (i0 + j < n) v[i0 + j] = (T)at;
+    at += x[j];
+  }
+  if (t == 255) sums[blockIdx.x] = s_sum[255];
+}
+
+// v[i] += offs[tile of i]
+template <typename T>
+__global__ __launch_bounds__(256) void wire_scan_add_kernel(T* __restrict__ v, const uint64_t* __restrict__ offs, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) v[i] += (T)offs[i / kWireScanTile];
+}
+
+// The entry counts of the scan's levels: [0] the table, then the tile totals of the level below,
+// down to a level of one entry, which ends up holding the grand total.
+static std::vector<int64_t> wire_scan_levels(int64_t n_seg) {
+  std::vector<int64_t> cnt{n_seg};
+  do cnt.push_back((cnt.back() + kWireScanTile - 1) / kWireScanTile);
+  while (cnt.back() > 1);
+  return cnt;
+}
+
+int64_t wire_scan_words(int64_t n_seg) {
+  int64_t words = 0;
+  const std::vector<int64_t> cnt = wire_scan_levels(n_seg);
+  for (size_t k = 1; k < cnt.size(); ++k) words += cnt[k];
+  return words;
+}
+
+// Sizes and starts: on return (in stream order) table[i] is segment i's start in units and
+// scan[wire_scan_words(n_seg) - 1] the units of all segments.  `scan`: wire_scan_words u64 words.
+int wire_pack_plan_impl(const WireSegDev* segs, int64_t n_seg, void* wire, uint64_t* scan, hipStream_t s) {
+  TK_CHECK_ARG(segs && wire && scan && n_seg > 0 && n_seg < ((int64_t)1 << 31) && ((uintptr_t)wire & 63) == 0,
+               "bad arguments");
+  const std::vector<int64_t> cnt = wire_scan_levels(n_seg);
+  const int top = (int)cnt.size() - 1;
+  std::vector<uint64_t*> lev(cnt.size(), nullptr);
+  for (int k = 1; k <= top; ++k) lev[k] = k == 1 ? scan : lev[k - 1] + cnt[k - 1];
+  uint32_t* table = (uint32_t*)wire;
+  TK_HIP(hipMemsetAsync(wire, 0, (size_t)wire_table_bytes(n_seg), s));
+  hipLaunchKernelGGL(wire_encode_kernel<kWireSize>, dim3((unsigned)n_seg), dim3(256), 0, s, segs, (uint32_t*)nullptr, table,
+                     (uint8_t*)nullptr, 0u);
+  TK_LAUNCH_CHECK();
+  hipLaunchKernelGGL(wire_scan_tile_kernel<uint32_t>, dim3((unsigned)cnt[1]), dim3(256), 0, s, table, lev[1], n_seg);
+  TK_LAUNCH_CHECK();
+  for (int k = 1; k < top; ++k) {
+    hipLaunchKernelGGL(wire_scan_tile_kernel<uint64_t>, dim3((unsigned)cnt[k + 1]), dim3(256), 0, s, lev[k], lev[k + 1],
+                       cnt[k]);
+    TK_LAUNCH_CHECK();
+  }
+  for (int k = top - 2; k >= 1; --k) {
+    hipLaunchKernelGGL(wire_scan_add_kernel<uint64_t>, dim3((unsigned)((cnt[k] + 255) / 256)), dim3(256), 0, s, lev[k],
+                       lev[k + 1], cnt[k]);
+    TK_LAUNCH_CHECK();
+  }
+  if (top >= 2) {
+    hipLaunchKernelGGL(wire_scan_add_kernel<uint32_t>, dim3((unsigned)((n_seg + 255) / 256)), dim3(256), 0, s, table,
+                       lev[1], n_seg);
+    TK_LAUNCH_CHECK();
+  }
+  return TK_OK;
+}
+
+// Stores every segment at the start the table states (wire_pack_plan_impl); wire_bytes bounds the stores.
+int wire_pack_place_impl(const WireSegDev* segs, int64_t n_seg, void* wire, int64_t wire_bytes, hipStream_t s) {
+  const int64_t table = wire_table_bytes(n_seg);
+  TK_CHECK_ARG(segs && wire && n_seg > 0 && n_seg < ((int64_t)1 << 31) && ((uintptr_t)wire & 63) == 0 &&
+               wire_bytes >= table, "bad arguments");
+  const int64_t cap_units = std::min<int64_t>((wire_bytes - table) / 64, 0xFFFFFFF0ll);
+  hipLaunchKernelGGL(wire_encode_kernel<kWirePlace>, dim3((unsigned)n_seg), dim3(256), 0, s, segs, (uint32_t*)nullptr,
+                     (uint32_t*)wire, (uint8_t*)wire + table, (uint32_t)cap_units);
   TK_LAUNCH_CHECK();
   return TK_OK;
 }

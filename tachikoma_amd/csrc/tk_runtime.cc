@@ -13,6 +13,7 @@
 #include <cstring>
 #include <map>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -41,6 +42,9 @@ int host_copy_impl(const void* const* src, void* const* dst, const int64_t* byte
 int pack_records_impl(const void* table, int nrec, int64_t blocks, void* mirror, hipStream_t s);
 int wire_encode_impl(const WireSegDev* segs, int64_t n_seg, uint32_t* cursor, void* wire, int64_t wire_bytes,
                      hipStream_t s);
+int64_t wire_scan_words(int64_t n_seg);
+int wire_pack_plan_impl(const WireSegDev* segs, int64_t n_seg, void* wire, uint64_t* scan, hipStream_t s);
+int wire_pack_place_impl(const WireSegDev* segs, int64_t n_seg, void* wire, int64_t wire_bytes, hipStream_t s);
 int ewise_impl(const tk_tensor* x, const tk_tensor* r, tk_tensor* y, const tk_ewise_attrs* a, hipStream_t s);
 int conv2d_f32_impl(const tk_tensor* x, const tk_tensor* w, tk_tensor* y, const tk_conv2d_attrs* a, hipStream_t s);
 int dense_f32_impl(const tk_tensor* x, const tk_tensor* w, tk_tensor* y, hipStream_t s);
@@ -1537,5 +1541,85 @@ int tk_wire_encode_device(const tk_wire_record* recs, int n_recs, const void* co
   (void)hipFree(dev);
   return rc;
 }
+
+namespace {
+// Device scratch of tk_wire_pack_device (the segment list and the scan's levels): kept between
+// calls and only ever grown, because a trace job packs every chunk and hipFree would wait for the
+// previous chunk's copy.  One call at a time uses it.
+struct PackScratch {
+  std::mutex mu;
+  void* dev = nullptr;
+  int64_t bytes = 0;
+  int device = -1;
+};
+PackScratch g_pack_scratch;
+}  // namespace
+
+int64_t tk_wire_pack_device(const tk_wire_record* recs, int n_recs, const void* const* src, void* wire,
+                            int64_t wire_cap, void* stream) {
+  const int64_t bound = tk_wire_bound(recs, n_recs);
+  if (bound < 0) return bound;
+  if (!src || !wire || ((uintptr_t)wire & 63) != 0 || wire_cap < bound) {
+    tk::set_error("tk_wire_pack_device: the wire buffer is not 64-byte aligned or smaller than tk_wire_bound");
+    return TK_ERR_INVALID_ARG;
+  }
+  std::vector<int64_t> n(n_recs);
+  std::vector<int32_t> d(n_recs);
+  for (int i = 0; i < n_recs; ++i) n[i] = recs[i].n_elems, d[i] = recs[i].diff != 0;
+  std::vector<tk::WireSegRef> refs;
+  std::vector<tk::WireUnit> units;
+  tk::wire_layout(n.data(), d.data(), n_recs, &refs, &units);
+  if (refs.size() >= ((size_t)1 << 31)) {
+    tk::set_error("tk_wire_pack_device: too many segments");
+    return TK_ERR_UNSUPPORTED;
+  }
+  std::vector<tk::WireSegDev> segs;
+  segs.reserve(refs.size());
+  for (const tk::WireSegRef& r : refs) {
+    const int64_t e0 = tk::wire_elem_bytes(recs[r.rec].kind) * r.e0;
+    segs.push_back({(const char*)src[r.rec] + e0, recs[r.rec].diff ? (const char*)src[r.rec - 1] + e0 : nullptr, r.n,
+                    recs[r.rec].kind});
+  }
+  const int64_t n_seg = (int64_t)segs.size();
+  const int64_t table = tk::wire_table_bytes(n_seg);
+  const int64_t seg_bytes = tk::wire_align(n_seg * (int64_t)sizeof(tk::WireSegDev), 64);
+  const int64_t words = tk::wire_scan_words(n_seg);
+  hipStream_t s = tk::as_stream(stream);
+  std::lock_guard<std::mutex> lock(g_pack_scratch.mu);
+  int device = 0;
+  TK_HIP(hipGetDevice(&device));
+  if (g_pack_scratch.device != device || g_pack_scratch.bytes < seg_bytes + 8 * words) {
+    if (g_pack_scratch.dev) (void)hipFree(g_pack_scratch.dev);
+    g_pack_scratch.dev = nullptr, g_pack_scratch.bytes = 0;
+    TK_HIP(hipMalloc(&g_pack_scratch.dev, (size_t)(seg_bytes + 8 * words)));
+    g_pack_scratch.bytes = seg_bytes + 8 * words, g_pack_scratch.device = device;
+  }
+  const tk::WireSegDev* dev_segs = (const tk::WireSegDev*)g_pack_scratch.dev;
+  uint64_t* scan = (uint64_t*)((char*)g_pack_scratch.dev + seg_bytes);
+  TK_HIP(hipMemcpyAsync(g_pack_scratch.dev, segs.data(), segs.size() * sizeof(tk::WireSegDev), hipMemcpyHostToDevice, s));
+  int rc = tk::wire_pack_plan_impl(dev_segs, n_seg, wire, scan, s);
+  if (rc != TK_OK) return rc;
+  uint64_t total = 0;  // payload units; the copy returns once the value is here
+  TK_HIP(hipMemcpyAsync(&total, scan + words - 1, sizeof(total), hipMemcpyDeviceToHost, s));
+  TK_HIP(hipStreamSynchronize(s));
+  if (total > 0xFFFFFFF0ull) {
+    tk::set_error("tk_wire_pack_device: the packed records do not fit the format's 32-bit segment starts");
+    return TK_ERR_UNSUPPORTED;
+  }
+  const int64_t used = table + 64 * (int64_t)total;
+  if (used > bound) {
+    tk::set_error("tk_wire_pack_device: the segment sizes exceed tk_wire_bound");
+    return TK_ERR_HIP;
+  }
+  rc = tk::wire_pack_place_impl(dev_segs, n_seg, wire, used, s);
+  if (rc != TK_OK) return rc;
+  if (hipStreamSynchronize(s) != hipSuccess) {
+    tk::set_error("tk_wire_pack_device: the place kernel failed");
+    return TK_ERR_HIP;
+  }
+  return used;
+}
+
+int tk_wire_pack_tile(void) { return tk::kWireScanTile; }
 
 }  // extern "C"

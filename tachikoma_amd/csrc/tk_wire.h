@@ -39,6 +39,8 @@ namespace tk {
 constexpr int kWireBlock = 256;
 constexpr int kWireSegBlocks = 64;
 constexpr int kWireSegElems = kWireBlock * kWireSegBlocks;
+// entries one workgroup scans in the packer's prefix sum over the segment sizes (tk_wire_pack_device)
+constexpr int kWireScanTile = 2048;
 
 inline int64_t wire_align(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 inline int64_t wire_table_bytes(int64_t n_seg) { return wire_align(4 * n_seg, 64); }

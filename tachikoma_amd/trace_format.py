@@ -84,6 +84,13 @@ class TraceLayout:
                                               ctypes.c_void_p(image_ptr), image_size), "tk_trace_write_headers")
 
 
+def head_layout(json_text: str, params) -> Tuple[TraceLayout, int]:
+    """Layout of a trace file's head (header, json, params blob) and where its records section
+    starts; the same for both file versions."""
+    layout = TraceLayout.compute(json_text, params, [])
+    return layout, layout.total - int(_lib.load().tk_ndlist_layout(None, 0, None))
+
+
 def save_ndarray_list(arrays: Dict[str, np.ndarray]) -> bytes:
     """NDArray-list blob (``SaveParams``, src/runtime/file_utils.cc:210-236) of host arrays, in
     insertion order, written through the C ABI (tk_ndlist_layout / tk_ndlist_write_headers)."""
@@ -168,15 +175,31 @@ class Trace:
     records: Dict[str, np.ndarray]
 
 
-def read_trace(path_or_bytes, copy: bool = False) -> Trace:
-    if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
-        buf = path_or_bytes
-    else:
-        with open(path_or_bytes, "rb") as f:
-            buf = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+def _open(path_or_bytes):
+    if isinstance(path_or_bytes, (bytes, bytearray, memoryview, mmap.mmap)):
+        return path_or_bytes
+    with open(path_or_bytes, "rb") as f:
+        if os.fstat(f.fileno()).st_size == 0:
+            raise ValueError("not a tachikoma trace (empty file)")
+        return mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+
+
+def _header(buf):
+    if len(buf) < 56:
+        raise ValueError("not a tachikoma trace (shorter than its header)")
     magic, version, jl, po, ps, ro, rs = struct.unpack_from("<7Q", buf, 0)
     if magic != TRACE_MAGIC:
         raise ValueError("not a tachikoma trace (bad magic)")
+    return version, jl, po, ps, ro, rs
+
+
+def read_trace(path_or_bytes, copy: bool = False) -> Trace:
+    """The trace of a file of either version (a packed file is expanded first: unpack_trace)."""
+    buf = _open(path_or_bytes)
+    version, jl, po, ps, ro, rs = _header(buf)
+    if version == PACKED_VERSION:
+        buf = unpack_trace(buf)
+        version, jl, po, ps, ro, rs = _header(buf)
     if version != TRACE_VERSION:
         raise ValueError(f"unsupported trace version {version}")
     meta = json.loads(bytes(buf[56:56 + jl]).decode())
@@ -230,6 +253,7 @@ def records_digest(records: "Dict[str, np.ndarray] | Sequence[np.ndarray]") -> i
 
 
 def trace_file_digest(path_or_bytes) -> int:
+    """Digest of the records of a trace file of either version."""
     return records_digest(read_trace(path_or_bytes).records)
 
 
@@ -248,3 +272,309 @@ def trace_bytes(meta: Dict[str, Any], params: Dict[str, np.ndarray], records: Di
             raw = np.ascontiguousarray(v).reshape(-1).view(np.uint8)
             blob[off:off + raw.size] = raw.tobytes()
     return bytes(blob)
+
+
+# ---------------------------------------------------------------- packed trace files (version 2)
+# A packed file holds the records in the trace wire coding (include/tachikoma.h, "wire format")
+# instead of the NDArray-list blob.  Header, json and params blob are those of the version-1 file of
+# the same run (only `version` and `records_size` differ); the records section is
+#
+#     u32 "TKPK" | u32 n_records | u64 plan_len | u64 wire_size | u64 raw_size
+#     plan       one entry per record, in trace order:
+#                u16 name_len, name, u8 dtype code, u8 dtype bits, u8 ndim, u8 coding, u8 diff,
+#                ndim x i64 shape, and for a raw record u64 offset, u64 size (within the raw part)
+#     pad to 8
+#     wire       what tk_wire_encode_host writes for the coded records, in trace order
+#     raw        the payloads of the records the wire does not code
+#
+# coding is the wire kind (0 int32, 1 int8, 2 uint8) or RAW; diff says the record is differenced
+# against (int32) or clamp-predicted from (1-byte) the record before it.  The reader follows the
+# stored plan and never calls plan_records, so the rule below may change without breaking a file.
+# Nothing is padded beyond 8 bytes: a packed file is never larger than the version-1 file plus the
+# wire's worst case (tk_wire_bound) minus the bytes of the coded records.
+
+PACKED_VERSION = 2
+PACK_MAGIC = 0x4B504B54  # "TKPK"
+RAW = 255
+WIRE_KIND = {"int32": 0, "int8": 1, "uint8": 2}
+_SECTION = struct.Struct("<IIQQQ")
+
+
+def _align(x: int, a: int) -> int:
+    return (x + a - 1) // a * a
+
+
+def _n_elems(shape) -> int:
+    n = 1
+    for d in shape:
+        n *= int(d)
+    return n
+
+
+def plan_records(records: Sequence[Tuple[str, Sequence[int], str]]) -> List[Tuple[int, int]]:
+    """The planning rule of packed files, (coding, diff) per record, from the record list alone
+    (dtype, shape, order): an int32 record is wire kind 0, differenced when the record before it is a
+    coded int32 record of the same shape; an int8 / uint8 record is kind 1 / 2, clamp-predicted when
+    the record before it has the same kind and shape (blocks the clamp does not reproduce escape to a
+    raw plane, so no node attributes are needed); every other dtype, and an empty record, is RAW.
+    Both packers (GraphModule.dump_trace(packed=True) on the device, pack_trace on the host) use it."""
+    plan: List[Tuple[int, int]] = []
+    for i, (_, shape, dtype) in enumerate(records):
+        kind = WIRE_KIND.get(str(np.dtype(dtype)), RAW)
+        if kind != RAW and not 1 <= _n_elems(shape) <= 1 << 40:
+            kind = RAW
+        diff = int(kind != RAW and i > 0 and plan[i - 1][0] == kind and
+                   tuple(int(d) for d in records[i - 1][1]) == tuple(int(d) for d in shape))
+        plan.append((kind, diff))
+    return plan
+
+
+@dataclass
+class PackedEntry:
+    name: str
+    shape: Tuple[int, ...]
+    dtype: str
+    coding: int
+    diff: int
+    raw_off: int = 0
+    raw_size: int = 0
+
+    @property
+    def nbytes(self) -> int:
+        return _n_elems(self.shape) * np.dtype(self.dtype).itemsize
+
+
+def packed_entries(records, plan=None) -> List[PackedEntry]:
+    """Plan entries of a record list (raw payloads laid out in trace order)."""
+    plan = plan_records(records) if plan is None else plan
+    out, raw = [], 0
+    for (name, shape, dtype), (coding, diff) in zip(records, plan):
+        e = PackedEntry(name, tuple(int(d) for d in shape), str(np.dtype(dtype)), int(coding), int(diff))
+        if coding == RAW:
+            e.raw_off, e.raw_size = raw, e.nbytes
+            raw += e.raw_size
+        out.append(e)
+    return out
+
+
+def _plan_bytes(entries: Sequence[PackedEntry]) -> bytes:
+    out = bytearray()
+    for e in entries:
+        nm = e.name.encode()
+        d = _lib.dtype_struct(e.dtype)
+        out += struct.pack("<H", len(nm)) + nm + struct.pack("<5B", d.code, d.bits, len(e.shape), e.coding, e.diff)
+        out += struct.pack(f"<{len(e.shape)}q", *e.shape)
+        if e.coding == RAW:
+            out += struct.pack("<QQ", e.raw_off, e.raw_size)
+    return bytes(out)
+
+
+def _parse_plan(mv, off: int, end: int, n: int) -> List[PackedEntry]:
+    entries = []
+    for _ in range(n):
+        if off + 2 > end:
+            raise ValueError("truncated coding plan")
+        (ln,) = struct.unpack_from("<H", mv, off)
+        off += 2
+        if off + ln + 5 > end:
+            raise ValueError("truncated coding plan")
+        name = bytes(mv[off:off + ln]).decode()
+        code, bits, ndim, coding, diff = struct.unpack_from("<5B", mv, off + ln)
+        off += ln + 5
+        if off + 8 * ndim + (16 if coding == RAW else 0) > end:
+            raise ValueError("truncated coding plan")
+        shape = struct.unpack_from(f"<{ndim}q", mv, off)
+        off += 8 * ndim
+        if code not in (0, 1, 2) or bits not in (8, 16, 32, 64) or any(d < 0 for d in shape):
+            raise ValueError(f"record {name}: bad dtype or shape in the coding plan")
+        e = PackedEntry(name, tuple(shape), str(_np_dtype(code, bits)), coding, diff)
+        if coding == RAW:
+            e.raw_off, e.raw_size = struct.unpack_from("<QQ", mv, off)
+            off += 16
+        entries.append(e)
+    return entries
+
+
+def _wire_records(entries: Sequence[PackedEntry], offsets: Sequence[int]):
+    """tk_wire_record array of the coded entries (offsets: each entry's payload offset in the image)."""
+    coded = [(e, o) for e, o in zip(entries, offsets) if e.coding != RAW]
+    arr = (_lib.tk_wire_record * max(1, len(coded)))()
+    for i, (e, o) in enumerate(coded):
+        arr[i].offset, arr[i].n_elems, arr[i].diff, arr[i].kind = int(o), _n_elems(e.shape), e.diff, e.coding
+    return arr, len(coded)
+
+
+def packed_section_head(entries: Sequence[PackedEntry], wire_size: int) -> bytes:
+    """The records section of a packed file up to the wire: section header, plan, pad to 8."""
+    plan = _plan_bytes(entries)
+    raw_size = sum(e.raw_size for e in entries)
+    head = _SECTION.pack(PACK_MAGIC, len(entries), len(plan), wire_size, raw_size) + plan
+    return head + b"\0" * (_align(len(head), 8) - len(head))
+
+
+def _ptr(buf) -> Tuple[int, np.ndarray]:
+    a = np.frombuffer(buf, dtype=np.uint8)
+    return a.ctypes.data, a
+
+
+def pack_trace(path_or_bytes) -> bytes:
+    """The host packer: the packed (version 2) file of a version-1 trace file, built on
+    tk_wire_encode_host.  Compresses existing files without a GPU, and gives byte for byte what
+    GraphModule.dump_trace(packed=True) writes for the same run."""
+    buf = _open(path_or_bytes)
+    version, jl, po, ps, ro, rs = _header(buf)
+    if version != TRACE_VERSION:
+        raise ValueError(f"pack_trace wants a version-{TRACE_VERSION} trace, not version {version}")
+    if not 56 + jl <= po <= po + ps <= ro <= ro + rs <= len(buf):
+        raise ValueError("truncated trace file")
+    lib = _lib.load()
+    records = parse_ndarray_list(buf, ro, rs)
+    base, keep = _ptr(buf)
+    items = [(k, v.shape, str(v.dtype)) for k, v in records.items()]
+    offsets = [(v.ctypes.data - base) if v.size else ro for v in records.values()]
+    entries = packed_entries(items)
+    recs, n = _wire_records(entries, offsets)
+    wire = b""
+    if n:
+        bound = lib.tk_wire_bound(recs, n)
+        if bound < 0:
+            _lib.check(int(bound), "tk_wire_bound")
+        out = np.empty(bound, np.uint8)
+        used = lib.tk_wire_encode_host(recs, n, ctypes.c_void_p(base), len(buf), ctypes.c_void_p(out.ctypes.data), bound)
+        if used < 0:
+            _lib.check(int(used), "tk_wire_encode_host")
+        wire = out[:used].tobytes()
+    head = packed_section_head(entries, len(wire))
+    raws = [v.tobytes() for e, v in zip(entries, records.values()) if e.coding == RAW]
+    section = head + wire + b"".join(raws)
+    del keep
+    return (struct.pack("<7Q", TRACE_MAGIC, PACKED_VERSION, jl, po, ps, ro, len(section)) + bytes(buf[56:ro]) + section)
+
+
+@dataclass
+class PackedFile:
+    """A parsed packed file: offsets are absolute."""
+    json_text: str
+    params_off: int
+    params_size: int
+    entries: List[PackedEntry]
+    wire_off: int
+    wire_size: int
+    raw_off: int
+    raw_size: int
+    size: int
+
+
+def parse_packed(buf) -> PackedFile:
+    """Header, sections and coding plan of a packed file, every extent checked against the buffer."""
+    version, jl, po, ps, ro, rs = _header(buf)
+    if version != PACKED_VERSION:
+        raise ValueError(f"not a packed (version {PACKED_VERSION}) trace: version {version}")
+    size = len(buf)
+    if not 56 + jl <= po <= po + ps <= ro <= ro + rs <= size or rs < _SECTION.size:
+        raise ValueError("truncated packed trace file")
+    try:
+        json_text = bytes(buf[56:56 + jl]).decode()
+        magic, n, plan_len, wire_size, raw_size = _SECTION.unpack_from(buf, ro)
+        if magic != PACK_MAGIC:
+            raise ValueError("packed trace: bad records section")
+        wire_off = ro + _align(_SECTION.size + plan_len, 8)
+        if wire_off + wire_size + raw_size != ro + rs or n > plan_len:
+            raise ValueError("truncated packed trace file (sections do not add up)")
+        entries = _parse_plan(memoryview(buf), ro + _SECTION.size, ro + _SECTION.size + plan_len, n)
+    except (struct.error, UnicodeDecodeError) as e:
+        raise ValueError(f"packed trace: {e}") from None
+    for i, e in enumerate(entries):
+        if e.coding == RAW:
+            if e.raw_size != e.nbytes or e.raw_off + e.raw_size > raw_size:
+                raise ValueError(f"record {e.name}: raw payload outside the file")
+        elif (WIRE_KIND.get(e.dtype) != e.coding or not 1 <= _n_elems(e.shape) <= 1 << 40 or e.diff not in (0, 1) or
+              (e.diff and (i == 0 or entries[i - 1].coding != e.coding or
+                           _n_elems(entries[i - 1].shape) != _n_elems(e.shape)))):
+            raise ValueError(f"record {e.name}: coding {e.coding} / diff {e.diff} does not fit the record list")
+    return PackedFile(json_text, po, ps, entries, wire_off, wire_size, wire_off + wire_size, raw_size, size)
+
+
+def unpack_trace(path_or_bytes) -> bytearray:
+    """Exactly the version-1 file dump_trace writes for the same run, byte for byte (a bytearray: it
+    compares equal to the file's bytes and is not copied again).  The version-1 layout and headers
+    are a function of the json, the params blob and the plan's names / dtypes / shapes
+    (tk_trace_layout / tk_trace_write_headers); the coded records are expanded by tk_wire_decode, as
+    the stored plan says.  Raises ValueError on a truncated or corrupted file and reads nothing
+    outside it."""
+    buf = _open(path_or_bytes)
+    pf = parse_packed(buf)
+    lib = _lib.load()
+    params = parse_ndarray_list(buf, pf.params_off, pf.params_size)
+    p_items = [(k, v.shape, str(v.dtype)) for k, v in params.items()]
+    r_items = [(e.name, e.shape, e.dtype) for e in pf.entries]
+    # a width-0 block spends 5 bytes on 256 int32 elements: nothing expands further than that
+    if sum(e.nbytes for e in pf.entries) > 256 * pf.size + (1 << 20):
+        raise ValueError("packed trace: the plan's records cannot come from a file this small")
+    try:
+        layout = TraceLayout.compute(pf.json_text, p_items, r_items)
+    except _lib.TachikomaError as e:
+        raise ValueError(f"packed trace: {e}") from None
+    image = bytearray(layout.total)
+    cbuf = (ctypes.c_char * len(image)).from_buffer(image)
+    try:
+        layout.write_headers(ctypes.addressof(cbuf), len(image))
+        po = _align(56 + len(pf.json_text.encode()), TRACE_ALIGN)
+        if po != pf.params_off or po + pf.params_size > len(image):
+            raise ValueError("packed trace: the params blob does not lie where the header says")
+        image[po:po + pf.params_size] = buf[pf.params_off:pf.params_off + pf.params_size]
+        recs, n = _wire_records(pf.entries, layout.record_offsets)
+        if n:
+            base, keep = _ptr(buf)
+            rc = lib.tk_wire_decode(recs, n, ctypes.c_void_p(base + pf.wire_off), pf.wire_size,
+                                    ctypes.c_void_p(ctypes.addressof(cbuf)), len(image), 0)
+            del keep
+            if rc != 0:
+                raise ValueError("packed trace: " + lib.tk_last_error().decode(errors="replace"))
+        elif pf.wire_size:
+            raise ValueError("packed trace: a wire buffer without coded records")
+        for e, off in zip(pf.entries, layout.record_offsets):
+            if e.coding == RAW:
+                image[off:off + e.raw_size] = buf[pf.raw_off + e.raw_off:pf.raw_off + e.raw_off + e.raw_size]
+    finally:
+        del cbuf
+    return image
+
+
+def packed_info(path_or_bytes) -> Dict[str, Any]:
+    """Sizes and the coding plan of a packed file (``python -m tachikoma_amd.trace_format info``)."""
+    pf = parse_packed(_open(path_or_bytes))
+    coded = sum(e.nbytes for e in pf.entries if e.coding != RAW)
+    return {"version": PACKED_VERSION, "file_bytes": pf.size, "records": len(pf.entries), "wire_bytes": pf.wire_size,
+            "coded_record_bytes": coded, "raw_record_bytes": pf.raw_size,
+            "plan": [{"name": e.name, "dtype": e.dtype, "shape": list(e.shape),
+                      "coding": "raw" if e.coding == RAW else e.coding, "diff": e.diff} for e in pf.entries]}
+
+
+def main(argv=None) -> int:
+    import argparse
+    p = argparse.ArgumentParser(prog="python -m tachikoma_amd.trace_format",
+                                description="Pack, unpack or describe tachikoma trace files.")
+    sub = p.add_subparsers(dest="cmd", required=True)
+    for name, text in (("pack", "version-1 file -> packed file"), ("unpack", "packed file -> version-1 file")):
+        q = sub.add_parser(name, help=text)
+        q.add_argument("src")
+        q.add_argument("dst")
+    sub.add_parser("info", help="sizes and coding plan of a file").add_argument("src")
+    args = p.parse_args(argv)
+    if args.cmd == "info":
+        version = _header(_open(args.src))[0]
+        info = packed_info(args.src) if version == PACKED_VERSION else \
+            {"version": version, "file_bytes": os.path.getsize(args.src), "records": len(read_trace(args.src).records)}
+        print(json.dumps(info, indent=1))
+        return 0
+    out = pack_trace(args.src) if args.cmd == "pack" else unpack_trace(args.src)
+    with open(args.dst, "wb") as f:
+        f.write(out)
+    print(f"{args.src}: {os.path.getsize(args.src)} -> {args.dst}: {len(out)} bytes")
+    return 0
+
+
+if __name__ == "__main__":
+    import sys
+    sys.exit(main())

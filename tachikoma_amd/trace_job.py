@@ -7,19 +7,25 @@ A rank's shard of the global sample range (``shard.shard_range``) is cut into ch
 ``<stem>.rank<r>.chunk<c>.tkt`` whose header carries the chunk's ``sample_offset``.  A
 chunk counts as done only once its file is complete on disk: the file is written under a
 ``.partial`` name, fsync'd and renamed, and then one JSON line
-``{"chunk", "sample_offset", "n_samples", "file", "bytes", "digest"}`` is appended (and
+``{"chunk", "sample_offset", "n_samples", "file", "bytes", "digest", "packed"}`` is appended (and
 fsync'd) to the rank's journal ``<stem>.rank<r>.journal``.  A restarted job replays the
 journal, keeps the chunks whose entry matches the plan and whose file still has the
 recorded size (and, with ``verify``, the recorded record digest), and traces the rest.  A
 crash at any point therefore loses at most the chunks in flight.
 
+With ``packed`` the chunk files are packed (version 2) trace files (trace_format.pack_trace /
+unpack_trace): same names, same manifest, same digests (the digest is of the records, not of the
+file), about half the bytes.  ``"packed"`` in a journal entry says which kind the file is, and a
+resumed job re-traces the chunks whose flag differs from its own.
+
 On the device the chunk files are produced by :class:`GraphModuleTracer`: two pinned trace
 images alternate, so chunk c's file is written by a host thread while chunk c+1 runs and
-its records are copied D2H (the bench's file sink, overlapped with the next batch).
+its records are copied D2H (the bench's file sink, overlapped with the next batch).  With
+``packed`` two device packers with their pinned stagings alternate instead (PackedCapture).
 
 CLI (one process per GPU, torch.distributed.run environment; rank 0 writes the manifest)::
 
-    python -m tachikoma_amd.trace_job --model resnet50 --samples 4096 --chunk 64 --out-dir DIR
+    python -m tachikoma_amd.trace_job --model resnet50 --samples 4096 --chunk 64 --out-dir DIR [--packed]
 """
 from __future__ import annotations
 
@@ -116,9 +122,11 @@ class Journal:
             os.remove(self.path)
 
 
-def _valid(entry: dict, c: Chunk, verify: bool) -> bool:
+def _valid(entry: dict, c: Chunk, verify: bool, packed: bool = False) -> bool:
     if (entry.get("sample_offset"), entry.get("n_samples"), entry.get("file")) != (c.sample_offset, c.n_samples,
                                                                                      os.path.basename(c.file)):
+        return False
+    if bool(entry.get("packed", False)) != packed:  # entries from before the flag are unpacked files
         return False
     try:
         if os.path.getsize(c.file) != entry.get("bytes"):
@@ -140,16 +148,19 @@ Tracer = Callable[[int, int, str], "concurrent.futures.Future[int]"]
 
 def run(tracer: Tracer, global_samples: int, chunk: int, out_dir: str, rank: int = 0, world: int = 1,
         resume: bool = True, verify: bool = False, stem: str = "trace",
-        log: Optional[Callable[[str], None]] = None) -> List[shard.ShardEntry]:
+        log: Optional[Callable[[str], None]] = None, packed: Optional[bool] = None) -> List[shard.ShardEntry]:
     """Trace this rank's chunks that are not done yet; returns the entries of ALL its chunks
-    (resumed and new) in sample order."""
+    (resumed and new) in sample order.  ``packed``: whether the tracer writes packed files (default:
+    the tracer's own ``packed`` attribute, else False); it is journalled, and chunks journalled with
+    the other value are traced again."""
+    packed = bool(getattr(tracer, "packed", False) if packed is None else packed)
     os.makedirs(out_dir, exist_ok=True)
     chunks = plan_chunks(global_samples, world, rank, chunk, out_dir, stem)
     journal = Journal(journal_file(out_dir, rank, stem))
     if not resume:
         journal.reset()
     done = journal.entries() if resume else {}
-    kept = {c.index: done[c.index] for c in chunks if c.index in done and _valid(done[c.index], c, verify)}
+    kept = {c.index: done[c.index] for c in chunks if c.index in done and _valid(done[c.index], c, verify, packed)}
     todo = [c for c in chunks if c.index not in kept]
     if log:
         log(f"rank {rank}: {len(chunks)} chunks, {len(kept)} done, {len(todo)} to trace")
@@ -163,7 +174,7 @@ def run(tracer: Tracer, global_samples: int, chunk: int, out_dir: str, rank: int
         os.replace(tmp, c.file)
         _fsync_dir(c.file)
         e = {"chunk": c.index, "sample_offset": c.sample_offset, "n_samples": c.n_samples,
-             "file": os.path.basename(c.file), "bytes": os.path.getsize(c.file), "digest": shard.hex64(digest)}
+             "file": os.path.basename(c.file), "bytes": os.path.getsize(c.file), "digest": shard.hex64(digest), "packed": packed}
         journal.append(e)
         kept[c.index] = e
 
@@ -191,13 +202,20 @@ def run(tracer: Tracer, global_samples: int, chunk: int, out_dir: str, rank: int
 
 class GraphModuleTracer:
     """Device tracer over built GraphModules (one per distinct chunk size): chunk c's pinned
-    image is written to its file by a writer thread while chunk c+1 runs on the GPU."""
+    image is written to its file by a writer thread while chunk c+1 runs on the GPU.
+
+    With ``packed`` the files are packed trace files: the runs are compute-only, and two packers
+    (a device wire buffer and a pinned staging each) alternate, so chunk c's copy and file write
+    overlap chunk c+1's kernels; the record buffers are free as soon as the pack call returns."""
 
     def __init__(self, build_module: Callable[[int], "object"], inputs: Callable[[int, int], "object"],
-                 model: str = "graph", input_name: str = "data", rank: int = 0, world: int = 1):
+                 model: str = "graph", input_name: str = "data", rank: int = 0, world: int = 1,
+                 packed: bool = False):
         self.build_module = build_module
         self.inputs = inputs
         self.model, self.input_name, self.rank, self.world = model, input_name, rank, world
+        self.packed = bool(packed)
+        self.stats: List[dict] = []  # packed: per chunk {"pack_ms", "copy_ms", "write_ms", "bytes"}
         self.modules: Dict[int, list] = {}  # n_samples -> [GraphModule, [TraceCapture x2], next slot]
         self.writer = concurrent.futures.ThreadPoolExecutor(max_workers=1)
         self.busy: Dict[int, "concurrent.futures.Future"] = {}
@@ -205,12 +223,13 @@ class GraphModuleTracer:
 
     def _module(self, n: int):
         if n not in self.modules:
-            from .contrib.graph_executor import TraceCapture
+            from .contrib.graph_executor import PackedCapture, TraceCapture
             m = self.build_module(n)
             # traced runs as one replayed HIP graph: one host call per chunk, so a host that issues
             # calls late cannot starve the copies (profiles/r03r_run_modes_slow_host.txt)
             m.module.use_graph = True
-            caps = [m.trace_capture(), TraceCapture(m.module, m._meta)]
+            caps = ([m.packed_capture(), PackedCapture(m.module, m._meta)] if self.packed else
+                    [m.trace_capture(), TraceCapture(m.module, m._meta)])
             self.modules[n] = [m, caps, 0]
         return self.modules[n]
 
@@ -229,8 +248,11 @@ class GraphModuleTracer:
         cap.update_meta(**meta)
         m.set_input(self.input_name, self.inputs(sample_offset, n_samples))
         stream = torch.cuda.current_stream(m.module.device)
-        cap.capture_inputs(stream)
-        m.module.run(stream, cap.capture_stream, cap.host_dst)
+        if self.packed:
+            m.module.run(stream)
+        else:
+            cap.capture_inputs(stream)
+            m.module.run(stream, cap.capture_stream, cap.host_dst)
         # device digest of exactly these records, copied on the stream into this image's own
         # pinned slot: the module's digest tensor is reused by the next chunk's run, which the
         # stream may reach before the writer thread reads the value
@@ -239,6 +261,8 @@ class GraphModuleTracer:
         if slot_t is None:
             slot_t = self.digest_slots[id(cap)] = torch.empty(digest.shape, dtype=digest.dtype, pin_memory=True)
         slot_t.copy_(digest, non_blocking=True)
+        if self.packed:
+            cap.pack(stream)  # waits for the run; the copy into the staging is on the packer's stream
         done = torch.cuda.Event()
         done.record(stream)
 
@@ -246,6 +270,8 @@ class GraphModuleTracer:
             done.synchronize()
             cap.synchronize()
             cap.write(path)
+            if self.packed:
+                self.stats.append(dict(cap.stats, bytes=cap.size))
             return int(slot_t.reshape(-1)[0].item()) & 0xFFFFFFFFFFFFFFFF
 
         fut = self.writer.submit(write)
@@ -271,6 +297,8 @@ def main(argv=None) -> int:
     p.add_argument("--out-dir", required=True)
     p.add_argument("--no-resume", action="store_true", help="start over (drop the journal)")
     p.add_argument("--verify", action="store_true", help="re-digest resumed chunk files")
+    p.add_argument("--packed", action="store_true",
+                   help="write packed (version 2) chunk files: the wire coding on disk, expanded on read")
     args = p.parse_args(argv)
     import torch
     from . import relay, zoo
@@ -290,11 +318,11 @@ def main(argv=None) -> int:
         return graph_executor.GraphModule(lib["default"](device.index))
 
     tracer = GraphModuleTracer(build_module, proto.sample_inputs, model=proto.name, input_name=proto.input_name,
-                               rank=rank, world=world)
+                               rank=rank, world=world, packed=args.packed)
     log = lambda s: print(f"[trace_job] {s}", file=sys.stderr, flush=True)  # noqa: E731
     try:
         entries = run(tracer, args.samples, args.chunk, args.out_dir, rank, world, resume=not args.no_resume,
-                      verify=args.verify, log=log)
+                      verify=args.verify, log=log, packed=args.packed)
     finally:
         tracer.close()
     if world > 1:
