@@ -736,6 +736,48 @@ int64_t tk_wire_pack_device(const tk_wire_record* recs, int n_recs, const void* 
 int tk_wire_pack_tile(void);
 int tk_wire_threads(void);
 
+/* The way back in: checking a wire buffer on the host, decoding it on the device.
+ *
+ * tk_wire_check: walks the table and every segment's header (bases, widths) of a host copy of a
+ * wire buffer and reads no payload.  TK_OK exactly when tk_wire_decode would accept the buffer: the
+ * records pass the rules above, the table lies inside wire_bytes, every segment's start, header and
+ * stated length lie inside the payload, and widths are <= 4 in an int32 segment and <= 1 in a
+ * 1-byte one; else TK_ERR_INVALID_ARG with tk_last_error.  It is the gate of the device decoder:
+ * upload only the very bytes it accepted.
+ *
+ * tk_wire_unpack_device: the device decoder.  `wire` is a device copy (64-byte aligned) of a buffer
+ * tk_wire_check accepted, dst[i] (a host array, one entry per record) the device buffer of record
+ * i, or NULL for a record that is decoded for its chain's sake only.  An int32 destination must be
+ * 4-byte aligned, a 1-byte one may have any alignment; 16-byte aligned ones take 16-byte stores.
+ * One workgroup walks a chain of diff-linked records segment by segment and keeps the decoded
+ * predecessor in registers: it is never read back from dst.  TK_WIRE_UNPACK_STORE writes the
+ * records.  TK_WIRE_UNPACK_COMPARE writes nothing and compares dst[i] with what the wire says
+ * record i is: report[i] (host, n_recs entries) receives the number of differing elements and the
+ * index of the first one (~0 if none); a wrong record does not make the record chained to it look
+ * wrong.  Segments may lie in any order (the table is followed).  The arguments are checked before
+ * any launch (kinds, counts, a diff record following a record of another size or kind, `wire` not
+ * 64-byte aligned, wire_bytes below the table size); a segment that leaves wire_bytes or states a
+ * width its kind does not have makes the call return TK_ERR_INVALID_ARG after the launch, with
+ * nothing read outside `wire` and the rest of that chain neither stored nor compared.
+ * Synchronises `stream`.
+ *
+ * tk_compare_device: n_elems elements of elem_bytes (1, 2, 4 or 8) bytes each in two device
+ * buffers of any alignment, compared bit for bit; *report as above, the index counted in elements.
+ * tk_compare_device_batch: n such pairs in one launch and one synchronisation, report[i] for pair
+ * i (pairs of no elements report equal). */
+typedef struct {
+  uint64_t mismatches;
+  uint64_t first; /* element index of the first mismatch, ~0 if none */
+} tk_wire_mismatch;
+enum { TK_WIRE_UNPACK_STORE = 0, TK_WIRE_UNPACK_COMPARE = 1 };
+int tk_wire_check(const tk_wire_record* recs, int n_recs, const void* wire, int64_t wire_bytes);
+int tk_wire_unpack_device(const tk_wire_record* recs, int n_recs, const void* wire, int64_t wire_bytes,
+                          void* const* dst, int mode, tk_wire_mismatch* report, void* stream);
+int tk_compare_device(const void* expected, const void* got, int64_t n_elems, int elem_bytes,
+                      tk_wire_mismatch* report, void* stream);
+int tk_compare_device_batch(const void* const* expected, const void* const* got, const int64_t* n_elems,
+                            const int32_t* elem_bytes, int n, tk_wire_mismatch* report, void* stream);
+
 /* Makes `stream` wait for the copies of the last traced run: call before writing any
  * tensor the module reads (GraphModule.set_input / load_params,
  * graph_executor.cc:158-166 SetInput) on a stream of your own. */

@@ -316,6 +316,17 @@ class tk_wire_record(ctypes.Structure):
     ]
 
 
+class tk_wire_mismatch(ctypes.Structure):
+    _fields_ = [
+        ("mismatches", ctypes.c_uint64),
+        ("first", ctypes.c_uint64),    # element index of the first mismatch, ~0 if none
+    ]
+
+
+TK_WIRE_UNPACK_STORE, TK_WIRE_UNPACK_COMPARE = 0, 1
+NO_MISMATCH = 0xFFFFFFFFFFFFFFFF
+
+
 class tk_array_meta(ctypes.Structure):
     _fields_ = [
         ("name", ctypes.c_char_p),
@@ -427,6 +438,13 @@ SIGNATURES = {
     "tk_wire_pack_device": (_I64, [ctypes.POINTER(tk_wire_record), ctypes.c_int, ctypes.POINTER(_VP), _VP, _I64, _VP]),
     "tk_wire_pack_tile": (ctypes.c_int, []),
     "tk_wire_threads": (ctypes.c_int, []),
+    "tk_wire_check": (ctypes.c_int, [ctypes.POINTER(tk_wire_record), ctypes.c_int, _VP, _I64]),
+    "tk_wire_unpack_device": (ctypes.c_int, [ctypes.POINTER(tk_wire_record), ctypes.c_int, _VP, _I64,
+                                             ctypes.POINTER(_VP), ctypes.c_int, ctypes.POINTER(tk_wire_mismatch), _VP]),
+    "tk_compare_device": (ctypes.c_int, [_VP, _VP, _I64, ctypes.c_int, ctypes.POINTER(tk_wire_mismatch), _VP]),
+    "tk_compare_device_batch": (ctypes.c_int, [ctypes.POINTER(_VP), ctypes.POINTER(_VP), ctypes.POINTER(_I64),
+                                               ctypes.POINTER(ctypes.c_int32), ctypes.c_int,
+                                               ctypes.POINTER(tk_wire_mismatch), _VP]),
     "tk_module_tune": (ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32),
                                       ctypes.POINTER(_F32)]),
     "tk_module_set_node_algo": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int]),

@@ -11,8 +11,10 @@ executor's per-node dump (python/tvm/contrib/debugger/debug_executor.py:210-347)
 from __future__ import annotations
 
 import json
+import os
 import time
-from typing import Any, Dict, List, Optional
+from dataclasses import dataclass
+from typing import Any, Dict, List, Optional, Tuple
 
 import numpy as np
 
@@ -225,6 +227,216 @@ class PackedCapture:
         return memoryview(self.image.numpy())[:self.size]
 
 
+@dataclass
+class Mismatch:
+    """One record of a trace file that the module's buffer does not equal."""
+    name: str
+    op: str                       # the op that produced the record ("input" for a graph input)
+    position: int                 # in trace order
+    dtype: str
+    shape: Tuple[int, ...]
+    count: int                    # differing elements
+    flat_index: int               # the first of them
+    first_index: Tuple[int, ...]  # the same, unravelled
+
+
+class VerifyReport:
+    """What GraphModule.verify_trace returns.  ``ok``: no record differs and the params are equal.
+    ``mismatches`` are in trace order, which is a topological order, so ``first`` (the earliest, or
+    None) is the first op whose recorded inputs all verified.  ``stats``: read_ms, upload_ms,
+    run_ms, compare_ms, file_bytes, upload_bytes, uploads, packed."""
+
+    def __init__(self, verifier, source, n_records, mismatches, params_differing, stats):
+        self._verifier, self._source = verifier, source
+        self.n_records = n_records
+        self.mismatches: List[Mismatch] = mismatches
+        self.params_differing: List[str] = params_differing
+        self.params_equal = not params_differing
+        self.ok = not mismatches and self.params_equal
+        self.first: Optional[Mismatch] = mismatches[0] if mismatches else None
+        self.stats = stats
+
+    def detail(self, m: Mismatch):
+        """(expected, got) at ``m.flat_index``: the file's value, through the host reader
+        (trace_format.read_trace: the slow path, meant for a failure only), and the value in the
+        module's buffer as it stands now (one small D2H copy)."""
+        expected = tf.read_trace(self._source).records[m.name].reshape(-1)[m.flat_index]
+        got = self._verifier.module.buffers[m.name].reshape(-1)[m.flat_index].item()
+        return expected.item(), got
+
+    def __repr__(self):
+        return (f"VerifyReport(ok={self.ok}, n_records={self.n_records}, mismatched={len(self.mismatches)}, "
+                f"first={self.first.name if self.first else None}, params_equal={self.params_equal})")
+
+
+class TraceVerifier:
+    """Checks trace files against a module on the device: a pinned staging a file is read into and
+    a device buffer its records section (packed: the wire and the raw payloads as they are; version
+    1: the records blob) and params blob are uploaded to.  Both are sized once for the module --
+    the file head plus tk_wire_bound plus the raw bytes, or the version-1 file, whichever is larger
+    -- and reused across files.  Nothing is uploaded that trace_format.check_trace (tk_wire_check
+    for the wire section) did not accept on the very bytes of the staging: a damaged file is a
+    ValueError on the host and the device never sees it.  The expected records are never
+    materialised: tk_wire_unpack_device compares the module's buffers against the wire as it
+    decodes it, tk_compare_device_batch compares what the wire does not code."""
+
+    ALIGN = 4096
+
+    def __init__(self, module: DeviceModule, meta: Dict[str, Any]):
+        import torch
+        self.module = module
+        self.lib = module.lib
+        plan = module.plan
+        self.params = [(t.name, t.shape, t.dtype) for t in plan.params]
+        self.records = [(t.name, t.shape, t.dtype) for t in plan.records]
+        self.ops = {o.name: o.op for o in plan.ops}
+        self.inputs = {t.name for t in plan.inputs}
+        text = tf.header_json(meta)
+        v1 = tf.TraceLayout.compute(text, self.params, self.records)
+        head, records_off = tf.head_layout(text, self.params)
+        entries = tf.packed_entries(self.records)
+        recs, n = tf._wire_records(entries, [0] * len(entries))
+        bound = int(self.lib.tk_wire_bound(recs, n)) if n else 0
+        if bound < 0:
+            _lib.check(bound, "tk_wire_bound")
+        raw = sum(e.raw_size for e in entries)
+        packed = records_off + len(tf.packed_section_head(entries, 0)) + bound + raw
+        # a file of the same graph from another job may carry a longer json: two pages of slack
+        self._alloc(max(v1.total, packed) + 2 * self.ALIGN)
+        self.uploads = 0  # H2D copies issued so far
+
+    def _alloc(self, size: int) -> None:
+        import torch
+        self.staging = torch.empty(size, dtype=torch.uint8, pin_memory=True)
+        self.device = torch.empty(size + self.ALIGN, dtype=torch.uint8, device=self.module.device)
+        self.host = self.staging.numpy()
+
+    def _read(self, source) -> int:
+        """The file's bytes into the staging; returns their count."""
+        if isinstance(source, (bytes, bytearray, memoryview)):
+            n = len(source)
+            if n > len(self.host):
+                self._alloc(n)
+            self.host[:n] = np.frombuffer(source, np.uint8)
+            return n
+        with open(source, "rb", buffering=0) as f:
+            n = os.fstat(f.fileno()).st_size
+            if n > len(self.host):
+                self._alloc(n)
+            got = 0
+            while got < n:
+                k = f.readinto(memoryview(self.host)[got:n])
+                if not k:
+                    break
+                got += k
+            return got
+
+    def stage(self, source):
+        """Read and check on the host: (CheckedTrace, stats).  Raises ValueError; uploads nothing."""
+        t0 = time.perf_counter()
+        n = self._read(source)
+        t1 = time.perf_counter()
+        ct = tf.check_trace(self.host[:n], self.records, self.params)
+        return ct, {"read_ms": (t1 - t0) * 1e3, "check_ms": (time.perf_counter() - t1) * 1e3, "file_bytes": n,
+                    "packed": ct.packed}
+
+    def upload(self, ct, stream, stats) -> None:
+        """Params blob at the front of the device buffer, records section behind it (each at a
+        4 KiB boundary, so a packed file's wire is 64-byte aligned): one H2D copy each."""
+        import torch
+        self.params_at = 0
+        self.records_at = (ct.params_size + self.ALIGN - 1) // self.ALIGN * self.ALIGN
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        with torch.cuda.stream(stream):
+            e0.record(stream)
+            for at, off, size in ((self.params_at, ct.params_off, ct.params_size),
+                                  (self.records_at, ct.records_off, ct.records_size)):
+                if size:
+                    self.device[at:at + size].copy_(self.staging[off:off + size], non_blocking=True)
+                    self.uploads += 1
+            e1.record(stream)
+        e1.synchronize()
+        stats["upload_ms"] = e0.elapsed_time(e1)
+        stats["upload_bytes"] = ct.params_size + ct.records_size
+        stats["uploads"] = self.uploads
+
+    def _expected_ptr(self, ct, e) -> int:
+        """Device address of a raw entry's payload."""
+        base = self.device.data_ptr() + self.records_at
+        return base + (ct.wire_size if ct.packed else 0) + e.raw_off
+
+    def _wire_call(self, ct, names, mode, stream):
+        """tk_wire_unpack_device over the coded records, with a destination for ``names`` only;
+        returns {name: (count, first)} in compare mode."""
+        import ctypes
+        coded = [e for e in ct.entries if e.coding != tf.RAW]
+        if not coded:
+            return {}
+        recs, n = tf._wire_records(ct.entries, [0] * len(ct.entries))
+        dst = (ctypes.c_void_p * n)(*[self.module.buffers[e.name].data_ptr() if e.name in names else None for e in coded])
+        report = (_lib.tk_wire_mismatch * n)()
+        _lib.check(self.lib.tk_wire_unpack_device(recs, n, ctypes.c_void_p(self.device.data_ptr() + self.records_at),
+                                                  ct.wire_size, dst, mode, report,
+                                                  ctypes.c_void_p(_lib.stream_handle(stream))), "tk_wire_unpack_device")
+        return {e.name: (int(r.mismatches), int(r.first)) for e, r in zip(coded, report) if e.name in names}
+
+    def _copy_raw(self, ct, names, stream) -> None:
+        """Device-to-device copies of the raw entries in ``names`` into the module's buffers."""
+        import torch
+        with torch.cuda.stream(stream):
+            for e in ct.entries:
+                if e.coding == tf.RAW and e.name in names and e.raw_size:
+                    at = self._expected_ptr(ct, e) - self.device.data_ptr()
+                    _as_bytes(self.module.buffers[e.name]).copy_(self.device[at:at + e.raw_size], non_blocking=True)
+
+    def store(self, ct, names, stream) -> None:
+        """The file's records ``names`` into the module's buffers (after the last traced run's
+        copies have read them: tk_module_wait_capture, as set_input does)."""
+        self.module.wait_capture(stream)
+        self._wire_call(ct, names, _lib.TK_WIRE_UNPACK_STORE, stream)
+        self._copy_raw(ct, names, stream)
+
+    def compare(self, ct, stream):
+        """({record name: (count, first)} over all records, [names of differing params])."""
+        import ctypes
+        names = {e.name for e in ct.entries}
+        out = self._wire_call(ct, names, _lib.TK_WIRE_UNPACK_COMPARE, stream)
+        pairs = [(e.name, self._expected_ptr(ct, e), self.module.buffers[e.name], e.raw_size, False)
+                 for e in ct.entries if e.coding == tf.RAW]
+        pbase = self.device.data_ptr() + self.params_at - ct.params_off
+        for name, shape, dtype, off in ct.params:
+            nbytes = tf._n_elems(shape) * np.dtype(dtype).itemsize
+            pairs.append((name, pbase + off, self.module.buffers[name], nbytes, True))
+        differing = []
+        if pairs:
+            n = len(pairs)
+            exp = (ctypes.c_void_p * n)(*[p[1] for p in pairs])
+            got = (ctypes.c_void_p * n)(*[p[2].data_ptr() for p in pairs])
+            cnt = (ctypes.c_int64 * n)(*[p[3] // p[2].element_size() for p in pairs])
+            es = (ctypes.c_int32 * n)(*[p[2].element_size() for p in pairs])
+            report = (_lib.tk_wire_mismatch * n)()
+            _lib.check(self.lib.tk_compare_device_batch(exp, got, cnt, es, n, report,
+                                                        ctypes.c_void_p(_lib.stream_handle(stream))),
+                       "tk_compare_device_batch")
+            for p, r in zip(pairs, report):
+                if p[4]:
+                    if r.mismatches:
+                        differing.append(p[0])
+                else:
+                    out[p[0]] = (int(r.mismatches), int(r.first))
+        return out, differing
+
+    def mismatches(self, ct, found) -> List[Mismatch]:
+        out = []
+        for pos, e in enumerate(ct.entries):
+            count, first = found.get(e.name, (0, _lib.NO_MISMATCH))
+            if count:
+                idx = tuple(int(i) for i in np.unravel_index(first, e.shape)) if e.shape else ()
+                out.append(Mismatch(e.name, "input" if e.name in self.inputs else self.ops.get(e.name, "?"), pos,
+                                    e.dtype, e.shape, count, first, idx))
+        return out
+
+
 class BenchmarkResult:
     """Runtimes from benchmarking, in seconds (python/tvm/runtime/module.py:34-98): ``results``
     and their mean / std / median / min / max."""
@@ -298,6 +510,7 @@ class GraphModule:
         self.plan = module.plan
         self._capture: Optional[TraceCapture] = None
         self._packed: Optional[PackedCapture] = None
+        self._verifier: Optional[TraceVerifier] = None
         self._meta = {"format": "tachikoma-trace", "version": tf.TRACE_VERSION, "model": "graph",
                       "target": "mi355x", "sample_offset": 0, "rank": 0, "world": 1,
                       "semantics": {"reference": "tvm llvm target without -mcpu", "requantize_compute_dtype":
@@ -320,6 +533,7 @@ class GraphModule:
         if self._packed is not None:
             self._packed.copy_stream.synchronize()
             self._packed = None
+        self._verifier = None
 
     def __enter__(self) -> "GraphModule":
         return self
@@ -544,6 +758,53 @@ class GraphModule:
         cap.synchronize()
         cap.write(path)
         return path
+
+    def trace_verifier(self) -> TraceVerifier:
+        if self._verifier is None:
+            self._verifier = TraceVerifier(self.module, self._meta)
+        return self._verifier
+
+    def verify_trace(self, path_or_bytes, run: bool = True) -> VerifyReport:
+        """Check a trace file of either version against this module, record by record, on the
+        device.  The file is read into pinned staging and checked on the host
+        (trace_format.check_trace: extents, the coding plan, tk_wire_check on the wire section, and
+        that its record list is this graph's; ValueError otherwise, before anything is uploaded).
+        One copy moves its records section to the device as it is, another its params.  With
+        ``run`` the file's graph-input records are put into the module's input buffers (the
+        decoder's store mode, after tk_module_wait_capture like set_input; the shadows conv nodes
+        read are rebuilt by the run itself) and the module runs once, compute only; with
+        ``run=False`` the buffers are compared as they stand.  Then tk_wire_unpack_device in
+        compare mode checks every coded record against the wire without ever expanding it,
+        tk_compare_device_batch the other records and the params."""
+        import torch
+        v = self.trace_verifier()
+        ct, stats = v.stage(path_or_bytes)
+        stream = torch.cuda.current_stream(self.module.device)
+        v.upload(ct, stream, stats)
+        t0 = time.perf_counter()
+        if run:
+            v.store(ct, {t.name for t in self.plan.inputs}, stream)
+            self.module.run(stream)
+            stream.synchronize()
+        t1 = time.perf_counter()
+        found, params_differing = v.compare(ct, stream)
+        stats["run_ms"] = (t1 - t0) * 1e3
+        stats["compare_ms"] = (time.perf_counter() - t1) * 1e3
+        return VerifyReport(v, path_or_bytes, len(ct.entries), v.mismatches(ct, found), params_differing, stats)
+
+    def load_trace(self, path_or_bytes) -> None:
+        """Put a trace file's records into the module's record buffers (the reading and the checks
+        of verify_trace, then the decoder's store mode and device-to-device copies), so that
+        get_node_output(name) returns what the file recorded.  Params are left alone.  The
+        shadows and other buffers derived from records are NOT rebuilt, and the next run()
+        overwrites every record."""
+        import torch
+        v = self.trace_verifier()
+        ct, stats = v.stage(path_or_bytes)
+        stream = torch.cuda.current_stream(self.module.device)
+        v.upload(ct, stream, stats)
+        v.store(ct, {e.name for e in ct.entries}, stream)
+        stream.synchronize()
 
     def trace_digest(self) -> int:
         """u64 digest of the last run's records, computed on the device

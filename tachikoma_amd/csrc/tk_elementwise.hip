@@ -1042,6 +1042,350 @@ int wire_pack_place_impl(const WireSegDev* segs, int64_t n_seg, void* wire, int6
   return TK_OK;
 }
 
+// ---------------------------------------------------------------- trace wire decoder
+// tk_wire_unpack_device: the way back in.  One workgroup owns a decode unit (tk_wire.h, WireUnit):
+// the same segment index of a chain of records linked by `diff`, walked in order.  The geometry is
+// the encoder's: 16 lanes own a block and 16 consecutive elements each, the 16 lane groups take
+// four passes over the segment's 64 blocks, and a lane's share of a full block's byte plane is one
+// 16-byte load.  Every segment's start comes from the table (segments may lie in any order: the
+// live encoder places them in completion order); the offsets of its block payloads come from the
+// widths by a prefix sum over the (<= 64) blocks, taken by the first wavefront and left in LDS.
+//
+// The decoded record stays in the registers it was decoded into (v[4][16]: a thread's 64 int32
+// values, or its 64 bytes as loaded in v[p][0..3]) and is the next record's predecessor: the int32
+// value the difference is added to, or the 16 bytes clamp(prev, lo, hi) is taken of (lo / hi from
+// base bytes 0 / 1, int8 through the sign-bit flip).  It is never read back from `dst`: in compare
+// mode `dst` holds the data under test, and a wrong record must not make the record chained to it
+// look wrong too.  A segment whose `dst` is null is decoded for the chain's sake only.
+//
+// kStore writes the records (16-byte stores; the short last block of a record and a destination
+// that is not 16-byte aligned go element by element) and uses no atomics.  kCompare loads the
+// destination's 16 elements instead and counts the elements that differ; the counts are reduced in
+// the workgroup, and only a workgroup that found one issues an atomicAdd on the record's count and
+// a 64-bit atomicMin on its first differing element, so an equal trace costs no atomic at all.  No
+// workgroup waits for another in either mode.
+//
+// The host refuses a wire buffer tk_wire_check does not accept before it is uploaded; all the same a
+// workgroup holds every segment to wire_seg_extent's rules (start, header and stated length inside
+// the payload, widths the kind has) before it reads a header or a plane, and on failure sets the
+// status word and stores and compares nothing more of its unit.
+enum { kWireStore = 0, kWireCompare = 1 };
+
+// Workgroup-wide sum of `cnt` and minimum of `first` into *out; every thread of the 256 calls it.
+// The atomics are issued by one thread, and only if some thread counted a mismatch.
+__device__ __forceinline__ void wire_report_mismatches(uint32_t cnt, unsigned long long first, tk_wire_mismatch* out,
+                                                       uint32_t* s_any, unsigned long long* s_red) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const bool mine = __any(cnt != 0);
+  if (lane == 0) s_any[wave] = mine;
+  __syncthreads();
+  if (s_any[0] | s_any[1] | s_any[2] | s_any[3]) {  // the same for the whole workgroup
+    unsigned long long c = cnt, f = first;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+      c += __shfl_xor(c, m, 64);
+      const unsigned long long o = __shfl_xor(f, m, 64);
+      f = o < f ? o : f;
+    }
+    if (lane == 0) s_red[wave] = c, s_red[4 + wave] = f;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      unsigned long long total = 0, lowest = ~0ull;
+      for (int w = 0; w < 4; ++w) total += s_red[w], lowest = s_red[4 + w] < lowest ? s_red[4 + w] : lowest;
+      atomicAdd(reinterpret_cast<unsigned long long*>(&out->mismatches), total);
+      atomicMin(reinterpret_cast<unsigned long long*>(&out->first), lowest);
+    }
+  }
+  __syncthreads();  // s_any / s_red are reused by the next record
+}
+
+template <int kMode>
+__global__ __launch_bounds__(256) void wire_decode_kernel(const WireUnitDev* __restrict__ units,
+                                                          const WireSegOut* __restrict__ segs,
+                                                          const uint32_t* __restrict__ table,
+                                                          const uint8_t* __restrict__ payload, int64_t payload_bytes,
+                                                          tk_wire_mismatch* report, uint32_t* status) {
+  __shared__ int32_t s_base[kWireSegBlocks];
+  __shared__ uint32_t s_w[kWireSegBlocks];
+  __shared__ uint32_t s_off[kWireSegBlocks];
+  __shared__ uint32_t s_bad;
+  __shared__ uint32_t s_any[4];
+  __shared__ unsigned long long s_red[8];
+  const WireUnitDev un = units[blockIdx.x];
+  const int n = un.n;
+  const int nb = (n + kWireBlock - 1) / kWireBlock;
+  const int g = threadIdx.x >> 4, l = threadIdx.x & 15;
+  const bool bytes = un.kind != kWireI32;
+  const uint32_t max_w = bytes ? 1u : 4u;
+  const uint32_t flip = un.kind == kWireI8 ? 0x80u : 0u;
+  const uint32_t base_bytes = (uint32_t)((4 * nb + 15) & ~15);
+  const uint32_t hdr = base_bytes + (uint32_t)((nb + 15) & ~15);
+  uint32_t v[4][16];  // the decoded record (1-byte kinds: v[p][0..3] hold the lane's 16 bytes)
+#pragma unroll
+  for (int p = 0; p < 4; ++p)
+#pragma unroll
+    for (int j = 0; j < 16; ++j) v[p][j] = 0;
+  for (int m = 0; m < un.count; ++m) {
+    const int64_t si = un.first + (int64_t)m * un.stride;
+    const int64_t off = (int64_t)table[si] * 64;
+    if (threadIdx.x == 0) s_bad = 0;
+    __syncthreads();  // also: the last record's readers of s_base / s_w / s_off are done
+    // start and header inside the payload, before any header byte is read (the same for every thread)
+    const bool head_ok = off <= payload_bytes && (int64_t)hdr <= payload_bytes - off;
+    const uint8_t* seg = payload + off;
+    if (head_ok && threadIdx.x < 64) {  // the first wavefront: widths, bases, prefix sum
+      const int b = threadIdx.x;
+      uint32_t w = 0, x = 0;
+      if (b < nb) {
+        w = seg[base_bytes + b];
+        s_base[b] = *reinterpret_cast<const int32_t*>(seg + 4 * b);
+        s_w[b] = w;
+        if (w > max_w) s_bad = 1, w = 0;
+        x = w * (uint32_t)min(kWireBlock, n - b * kWireBlock);
+      }
+      uint32_t incl = x;
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t y = (uint32_t)__shfl_up((int)incl, d, 64);
+        if (b >= d) incl += y;
+      }
+      if (b < nb) s_off[b] = hdr + incl - x;
+      // the stated length (at most 64 * 4 * 256 + hdr: no overflow) against what is left of the payload
+      if (b == 63 && (int64_t)(hdr + incl) > payload_bytes - off) s_bad = 1;
+    }
+    __syncthreads();
+    if (!head_ok || s_bad) {  // the same for every thread
+      if (threadIdx.x == 0) *status = 1;
+      return;
+    }
+    const WireSegOut so = segs[si];
+    const uint64_t e_seg = (uint64_t)un.e0;
+    uint32_t mis = 0, first = 0xFFFFFFFFu;  // the first differing element, counted within the segment
+    if (bytes) {
+      uint8_t* dst8 = static_cast<uint8_t*>(so.dst);
+      const bool aligned = ((uintptr_t)dst8 & 15) == 0;
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        const int b = p * 16 + g;
+        if (b >= nb) continue;
+        const int cnt = min(kWireBlock, n - b * kWireBlock);
+        const int e0 = b * kWireBlock + l * 16;
+        const int valid = min(16, n - e0);  // <= 0: the lane holds nothing
+        const uint32_t lo = (uint32_t)s_base[b] & 0xFFu, hi = ((uint32_t)s_base[b] >> 8) & 0xFFu;
+        if (s_w[b]) {  // the raw plane
+          const uint8_t* q = seg + s_off[b];
+          if (cnt == kWireBlock) {
+            const tk_v4i a = __builtin_nontemporal_load(reinterpret_cast<const tk_v4i*>(q + l * 16));
+            v[p][0] = (uint32_t)a.x, v[p][1] = (uint32_t)a.y, v[p][2] = (uint32_t)a.z, v[p][3] = (uint32_t)a.w;
+          } else {
+            v[p][0] = v[p][1] = v[p][2] = v[p][3] = 0;
+#pragma unroll
+            for (int j = 0; j < 16; ++j)
+              if (j < valid) v[p][j >> 2] |= (uint32_t)q[l * 16 + j] << (8 * (j & 3));
+          }
+        } else if (m > 0) {  // clamp of the predecessor, which v[p] still holds
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            uint32_t o = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+              const uint32_t x = ((v[p][c] >> (8 * k)) & 0xFFu) ^ flip;
+              o |= (min(max(x, lo ^ flip), hi ^ flip) ^ flip) << (8 * k);
+            }
+            v[p][c] = o;
+          }
+        } else {  // a constant block
+          v[p][0] = v[p][1] = v[p][2] = v[p][3] = lo * 0x01010101u;
+        }
+        if (!dst8 || valid <= 0) continue;
+        if (aligned && valid == 16) {
+          tk_v4i* d = reinterpret_cast<tk_v4i*>(dst8 + e0);
+          if constexpr (kMode == kWireStore) {
+            *d = tk_v4i{(int)v[p][0], (int)v[p][1], (int)v[p][2], (int)v[p][3]};
+          } else {
+            const tk_v4i a = *d;
+            const uint32_t got[4] = {(uint32_t)a.x, (uint32_t)a.y, (uint32_t)a.z, (uint32_t)a.w};
+            if (got[0] != v[p][0] || got[1] != v[p][1] || got[2] != v[p][2] || got[3] != v[p][3]) {
+#pragma unroll
+              for (int j = 15; j >= 0; --j)
+                if (wire_byte(got, j) != wire_byte(v[p], j)) ++mis, first = min(first, (uint32_t)(e0 + j));
+            }
+          }
+        } else {
+#pragma unroll
+          for (int j = 15; j >= 0; --j) {
+            if (j >= valid) continue;
+            if constexpr (kMode == kWireStore) dst8[e0 + j] = (uint8_t)wire_byte(v[p], j);
+            else if (dst8[e0 + j] != (uint8_t)wire_byte(v[p], j)) ++mis, first = min(first, (uint32_t)(e0 + j));
+          }
+        }
+      }
+    } else {
+      int32_t* dst32 = static_cast<int32_t*>(so.dst);
+      const bool aligned = ((uintptr_t)dst32 & 15) == 0;
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        const int b = p * 16 + g;
+        if (b >= nb) continue;
+        const int cnt = min(kWireBlock, n - b * kWireBlock);
+        const int e0 = b * kWireBlock + l * 16;
+        const int valid = min(16, n - e0);
+        const uint32_t w = s_w[b];
+        const uint8_t* q = seg + s_off[b];
+        uint32_t c[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) c[j] = 0;
+        for (uint32_t k = 0; k < w; ++k) {
+          uint32_t o[4] = {0, 0, 0, 0};
+          if (cnt == kWireBlock) {
+            const tk_v4i a = __builtin_nontemporal_load(reinterpret_cast<const tk_v4i*>(q + k * kWireBlock + l * 16));
+            o[0] = (uint32_t)a.x, o[1] = (uint32_t)a.y, o[2] = (uint32_t)a.z, o[3] = (uint32_t)a.w;
+          } else {
+#pragma unroll
+            for (int j = 0; j < 16; ++j)
+              if (j < valid) o[j >> 2] |= (uint32_t)q[k * cnt + l * 16 + j] << (8 * (j & 3));
+          }
+#pragma unroll
+          for (int j = 0; j < 16; ++j) c[j] |= wire_byte(o, j) << (8 * k);
+        }
+        const uint32_t base = (uint32_t)s_base[b];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) v[p][j] = (m > 0 ? v[p][j] : 0u) + base + c[j];  // int32 wrap-around
+        if (!dst32 || valid <= 0) continue;
+        if (aligned && valid == 16) {
+#pragma unroll
+          for (int q4 = 0; q4 < 4; ++q4) {
+            tk_v4i* d = reinterpret_cast<tk_v4i*>(dst32 + e0 + 4 * q4);
+            if constexpr (kMode == kWireStore) {
+              *d = tk_v4i{(int)v[p][4 * q4], (int)v[p][4 * q4 + 1], (int)v[p][4 * q4 + 2], (int)v[p][4 * q4 + 3]};
+            } else {
+              const tk_v4i a = *d;
+              const uint32_t got[4] = {(uint32_t)a.x, (uint32_t)a.y, (uint32_t)a.z, (uint32_t)a.w};
+#pragma unroll
+              for (int j = 3; j >= 0; --j)
+                if (got[j] != v[p][4 * q4 + j])
+                  ++mis, first = min(first, (uint32_t)(e0 + 4 * q4 + j));
+            }
+          }
+        } else {
+#pragma unroll
+          for (int j = 15; j >= 0; --j) {
+            if (j >= valid) continue;
+            if constexpr (kMode == kWireStore) dst32[e0 + j] = (int32_t)v[p][j];
+            else if ((uint32_t)dst32[e0 + j] != v[p][j]) ++mis, first = min(first, (uint32_t)(e0 + j));
+          }
+        }
+      }
+    }
+    if constexpr (kMode == kWireCompare) {
+      // so.dst is the same for every thread: all of them take part, or none
+      if (so.dst)
+        wire_report_mismatches(mis, first == 0xFFFFFFFFu ? ~0ull : (unsigned long long)(e_seg + first), report + so.rec,
+                               s_any, s_red);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void wire_report_init_kernel(tk_wire_mismatch* report, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) report[i].mismatches = 0, report[i].first = ~0ull;
+}
+
+// `report` (device, n_report entries) is reset on the stream first; `status` (device) must be zero.
+int wire_unpack_impl(const void* units, int64_t n_units, const void* segs, const void* wire, int64_t n_seg,
+                     int64_t wire_bytes, int mode, tk_wire_mismatch* report, int n_report, uint32_t* status,
+                     hipStream_t s) {
+  const int64_t table = wire_table_bytes(n_seg);
+  TK_CHECK_ARG(units && segs && wire && status && n_units > 0 && n_units < ((int64_t)1 << 31) &&
+               ((uintptr_t)wire & 63) == 0 && wire_bytes >= table && (mode == kWireStore || (report && n_report > 0)),
+               "bad arguments");
+  const uint8_t* payload = (const uint8_t*)wire + table;
+  if (mode == kWireStore) {
+    hipLaunchKernelGGL(wire_decode_kernel<kWireStore>, dim3((unsigned)n_units), dim3(256), 0, s,
+                       (const WireUnitDev*)units, (const WireSegOut*)segs, (const uint32_t*)wire, payload,
+                       wire_bytes - table, (tk_wire_mismatch*)nullptr, status);
+  } else {
+    hipLaunchKernelGGL(wire_report_init_kernel, dim3((unsigned)((n_report + 255) / 256)), dim3(256), 0, s, report, n_report);
+    TK_LAUNCH_CHECK();
+    hipLaunchKernelGGL(wire_decode_kernel<kWireCompare>, dim3((unsigned)n_units), dim3(256), 0, s,
+                       (const WireUnitDev*)units, (const WireSegOut*)segs, (const uint32_t*)wire, payload,
+                       wire_bytes - table, report, status);
+  }
+  TK_LAUNCH_CHECK();
+  return TK_OK;
+}
+
+// ---------------------------------------------------------------- raw compare
+// tk_compare_device: what the wire does not code (float32 / int16 / int64 records, version-1 files,
+// params) compared byte for byte, counted in elements.  One thread takes 16 bytes of a pair of
+// buffers: one 16-byte load of each where both pointers are 16-byte aligned, four dword loads where
+// both are 4-byte aligned, else (and for the pair's tail) byte loads; the mask of differing bytes
+// becomes a count of differing elements and the lowest of them.  A launch takes any number of pairs
+// (a workgroup finds its pair by binary search over the pairs' first workgroups) and reports as the
+// decoder's compare mode does: one atomicAdd and one atomicMin per workgroup that found a
+// difference, none otherwise.
+__global__ __launch_bounds__(256) void compare_kernel(const ComparePair* __restrict__ pairs, int n_pairs,
+                                                      tk_wire_mismatch* report) {
+  __shared__ uint32_t s_any[4];
+  __shared__ unsigned long long s_red[8];
+  int lo = 0, hi = n_pairs - 1;
+  const int64_t blk = blockIdx.x;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (pairs[mid].first_blk <= blk) lo = mid;
+    else hi = mid - 1;
+  }
+  const ComparePair pr = pairs[lo];
+  const int64_t at = ((blk - pr.first_blk) * 256 + threadIdx.x) * 16;
+  uint32_t mask = 0;  // bit i: byte at + i differs
+  if (at < pr.bytes) {
+    const uint8_t* a = pr.expected + at;
+    const uint8_t* b = pr.got + at;
+    const uintptr_t both = (uintptr_t)a | (uintptr_t)b;
+    if (at + 16 <= pr.bytes && (both & 3) == 0) {
+      uint32_t x[4], y[4];
+      if ((both & 15) == 0) {
+        const tk_v4i p = __builtin_nontemporal_load(reinterpret_cast<const tk_v4i*>(a));
+        const tk_v4i q = __builtin_nontemporal_load(reinterpret_cast<const tk_v4i*>(b));
+        x[0] = (uint32_t)p.x, x[1] = (uint32_t)p.y, x[2] = (uint32_t)p.z, x[3] = (uint32_t)p.w;
+        y[0] = (uint32_t)q.x, y[1] = (uint32_t)q.y, y[2] = (uint32_t)q.z, y[3] = (uint32_t)q.w;
+      } else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          x[c] = reinterpret_cast<const uint32_t*>(a)[c], y[c] = reinterpret_cast<const uint32_t*>(b)[c];
+      }
+      if (x[0] != y[0] || x[1] != y[1] || x[2] != y[2] || x[3] != y[3]) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) mask |= (uint32_t)(wire_byte(x, j) != wire_byte(y, j)) << j;
+      }
+    } else {
+      const int valid = (int)min((int64_t)16, pr.bytes - at);
+#pragma unroll
+      for (int j = 0; j < 16; ++j)
+        if (j < valid) mask |= (uint32_t)(a[j] != b[j]) << j;
+    }
+  }
+  uint32_t mis = 0;
+  unsigned long long first = ~0ull;
+  if (mask) {
+    const int es = pr.elem_bytes;
+    const uint32_t em = (1u << es) - 1u;
+    for (int e = 16 / es - 1; e >= 0; --e)
+      if ((mask >> (e * es)) & em) ++mis, first = (unsigned long long)(at / es + e);
+  }
+  wire_report_mismatches(mis, first, report + lo, s_any, s_red);
+}
+
+// pairs: device ComparePair[n_pairs] (first_blk filled, `blocks` their sum); report: device, n_pairs entries
+int compare_impl(const void* pairs, int n_pairs, int64_t blocks, tk_wire_mismatch* report, hipStream_t s) {
+  TK_CHECK_ARG(pairs && report && n_pairs > 0 && blocks > 0 && blocks < ((int64_t)1 << 31), "bad arguments");
+  hipLaunchKernelGGL(wire_report_init_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, s, report, n_pairs);
+  TK_LAUNCH_CHECK();
+  hipLaunchKernelGGL(compare_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const ComparePair*)pairs, n_pairs, report);
+  TK_LAUNCH_CHECK();
+  return TK_OK;
+}
+
 // ---------------------------------------------------------------- nn.pad
 // One thread per output element (its index decomposed over up to 6 dimensions, innermost first):
 // inside the data's range it copies data[i - before], else writes the pad value.

@@ -45,6 +45,10 @@ int wire_encode_impl(const WireSegDev* segs, int64_t n_seg, uint32_t* cursor, vo
 int64_t wire_scan_words(int64_t n_seg);
 int wire_pack_plan_impl(const WireSegDev* segs, int64_t n_seg, void* wire, uint64_t* scan, hipStream_t s);
 int wire_pack_place_impl(const WireSegDev* segs, int64_t n_seg, void* wire, int64_t wire_bytes, hipStream_t s);
+int wire_unpack_impl(const void* units, int64_t n_units, const void* segs, const void* wire, int64_t n_seg,
+                     int64_t wire_bytes, int mode, tk_wire_mismatch* report, int n_report, uint32_t* status,
+                     hipStream_t s);
+int compare_impl(const void* pairs, int n_pairs, int64_t blocks, tk_wire_mismatch* report, hipStream_t s);
 int ewise_impl(const tk_tensor* x, const tk_tensor* r, tk_tensor* y, const tk_ewise_attrs* a, hipStream_t s);
 int conv2d_f32_impl(const tk_tensor* x, const tk_tensor* w, tk_tensor* y, const tk_conv2d_attrs* a, hipStream_t s);
 int dense_f32_impl(const tk_tensor* x, const tk_tensor* w, tk_tensor* y, hipStream_t s);
@@ -1621,5 +1625,151 @@ int64_t tk_wire_pack_device(const tk_wire_record* recs, int n_recs, const void* 
 }
 
 int tk_wire_pack_tile(void) { return tk::kWireScanTile; }
+
+namespace {
+// Device scratch of tk_wire_unpack_device / tk_compare_device_batch (unit, segment or pair lists,
+// the report and the status word): kept between calls and only ever grown, as the packer's.
+PackScratch g_unpack_scratch;
+
+int unpack_scratch(int64_t bytes, char** out) {
+  int device = 0;
+  TK_HIP(hipGetDevice(&device));
+  if (g_unpack_scratch.device != device || g_unpack_scratch.bytes < bytes) {
+    if (g_unpack_scratch.dev) (void)hipFree(g_unpack_scratch.dev);
+    g_unpack_scratch.dev = nullptr, g_unpack_scratch.bytes = 0;
+    TK_HIP(hipMalloc(&g_unpack_scratch.dev, (size_t)bytes));
+    g_unpack_scratch.bytes = bytes, g_unpack_scratch.device = device;
+  }
+  *out = (char*)g_unpack_scratch.dev;
+  return TK_OK;
+}
+}  // namespace
+
+int tk_wire_unpack_device(const tk_wire_record* recs, int n_recs, const void* wire, int64_t wire_bytes,
+                          void* const* dst, int mode, tk_wire_mismatch* report, void* stream) {
+  const int64_t bound = tk_wire_bound(recs, n_recs);  // host_plan's rules
+  if (bound < 0) return (int)bound;
+  const bool compare = mode == TK_WIRE_UNPACK_COMPARE;
+  if (!wire || !dst || ((uintptr_t)wire & 63) != 0 || (mode != TK_WIRE_UNPACK_STORE && !compare) ||
+      (compare && !report)) {
+    tk::set_error("tk_wire_unpack_device: null argument, unknown mode or a wire buffer that is not 64-byte aligned");
+    return TK_ERR_INVALID_ARG;
+  }
+  for (int i = 0; i < n_recs; ++i)
+    if (recs[i].kind == tk::kWireI32 && ((uintptr_t)dst[i] & 3) != 0) {
+      tk::set_error("tk_wire_unpack_device: the buffer of int32 record " + std::to_string(i) + " is not 4-byte aligned");
+      return TK_ERR_INVALID_ARG;
+    }
+  std::vector<int64_t> n(n_recs);
+  std::vector<int32_t> d(n_recs);
+  for (int i = 0; i < n_recs; ++i) n[i] = recs[i].n_elems, d[i] = recs[i].diff != 0;
+  std::vector<tk::WireSegRef> refs;
+  std::vector<tk::WireUnit> units;
+  tk::wire_layout(n.data(), d.data(), n_recs, &refs, &units);
+  const int64_t n_seg = (int64_t)refs.size(), n_units = (int64_t)units.size();
+  if (n_seg >= ((int64_t)1 << 31)) {
+    tk::set_error("tk_wire_unpack_device: too many segments");
+    return TK_ERR_UNSUPPORTED;
+  }
+  if (wire_bytes < tk::wire_table_bytes(n_seg)) {
+    tk::set_error("tk_wire_unpack_device: the segment table does not lie inside the wire buffer");
+    return TK_ERR_INVALID_ARG;
+  }
+  std::vector<tk::WireSegOut> segs(refs.size());
+  for (size_t i = 0; i < refs.size(); ++i) {
+    const tk::WireSegRef& r = refs[i];
+    char* base = (char*)dst[r.rec];
+    segs[i] = {base ? base + tk::wire_elem_bytes(recs[r.rec].kind) * r.e0 : nullptr, r.rec, 0};
+  }
+  std::vector<tk::WireUnitDev> udev(units.size());
+  for (size_t u = 0; u < units.size(); ++u) {
+    const tk::WireSegRef& r = refs[units[u].first];
+    udev[u] = {units[u].first, units[u].stride, units[u].count, r.n, recs[r.rec].kind, 0, r.e0};
+  }
+  const int64_t seg_bytes = tk::wire_align(n_seg * (int64_t)sizeof(tk::WireSegOut), 64);
+  const int64_t unit_bytes = tk::wire_align(n_units * (int64_t)sizeof(tk::WireUnitDev), 64);
+  const int64_t rep_bytes = tk::wire_align((int64_t)n_recs * (int64_t)sizeof(tk_wire_mismatch), 64);
+  hipStream_t s = tk::as_stream(stream);
+  std::lock_guard<std::mutex> lock(g_unpack_scratch.mu);
+  char* dev = nullptr;
+  int rc = unpack_scratch(seg_bytes + unit_bytes + rep_bytes + 64, &dev);
+  if (rc != TK_OK) return rc;
+  tk_wire_mismatch* rep = (tk_wire_mismatch*)(dev + seg_bytes + unit_bytes);
+  uint32_t* status = (uint32_t*)(dev + seg_bytes + unit_bytes + rep_bytes);
+  TK_HIP(hipMemcpyAsync(dev, segs.data(), segs.size() * sizeof(tk::WireSegOut), hipMemcpyHostToDevice, s));
+  TK_HIP(hipMemcpyAsync(dev + seg_bytes, udev.data(), udev.size() * sizeof(tk::WireUnitDev), hipMemcpyHostToDevice, s));
+  TK_HIP(hipMemsetAsync(status, 0, sizeof(uint32_t), s));
+  rc = tk::wire_unpack_impl(dev + seg_bytes, n_units, dev, wire, n_seg, wire_bytes, mode, rep, n_recs, status, s);
+  if (rc != TK_OK) return rc;
+  uint32_t bad = 0;
+  if (compare) TK_HIP(hipMemcpyAsync(report, rep, (size_t)n_recs * sizeof(tk_wire_mismatch), hipMemcpyDeviceToHost, s));
+  TK_HIP(hipMemcpyAsync(&bad, status, sizeof(bad), hipMemcpyDeviceToHost, s));
+  if (hipStreamSynchronize(s) != hipSuccess) {
+    tk::set_error("tk_wire_unpack_device: the decode kernel failed");
+    return TK_ERR_HIP;
+  }
+  if (bad) {
+    tk::set_error("tk_wire_unpack_device: a segment does not lie inside the wire buffer or states a width its kind "
+                  "does not have (was the buffer checked with tk_wire_check?)");
+    return TK_ERR_INVALID_ARG;
+  }
+  return TK_OK;
+}
+
+int tk_compare_device_batch(const void* const* expected, const void* const* got, const int64_t* n_elems,
+                            const int32_t* elem_bytes, int n, tk_wire_mismatch* report, void* stream) {
+  if (!expected || !got || !n_elems || !elem_bytes || !report || n < 1) {
+    tk::set_error("tk_compare_device_batch: null argument or no pairs");
+    return TK_ERR_INVALID_ARG;
+  }
+  std::vector<tk::ComparePair> pairs;
+  std::vector<int> index;  // pair of the launch -> pair of the call (empty pairs are not launched)
+  int64_t blocks = 0;
+  for (int i = 0; i < n; ++i) {
+    const int es = elem_bytes[i];
+    if ((es != 1 && es != 2 && es != 4 && es != 8) || n_elems[i] < 0 || n_elems[i] > ((int64_t)1 << 40) ||
+        (n_elems[i] > 0 && (!expected[i] || !got[i]))) {
+      tk::set_error("tk_compare_device_batch: pair " + std::to_string(i) +
+                    " has a null buffer, a negative count or an element size other than 1, 2, 4, 8");
+      return TK_ERR_INVALID_ARG;
+    }
+    report[i].mismatches = 0, report[i].first = ~(uint64_t)0;
+    if (n_elems[i] == 0) continue;
+    const int64_t bytes = n_elems[i] * es;
+    pairs.push_back({(const uint8_t*)expected[i], (const uint8_t*)got[i], bytes, blocks, es, 0});
+    index.push_back(i);
+    blocks += (bytes + 4095) / 4096;
+  }
+  if (pairs.empty()) return TK_OK;
+  if (blocks >= ((int64_t)1 << 31)) {
+    tk::set_error("tk_compare_device_batch: too much to compare in one launch");
+    return TK_ERR_UNSUPPORTED;
+  }
+  const int np = (int)pairs.size();
+  const int64_t pair_bytes = tk::wire_align(np * (int64_t)sizeof(tk::ComparePair), 64);
+  hipStream_t s = tk::as_stream(stream);
+  std::lock_guard<std::mutex> lock(g_unpack_scratch.mu);
+  char* dev = nullptr;
+  int rc = unpack_scratch(pair_bytes + np * (int64_t)sizeof(tk_wire_mismatch), &dev);
+  if (rc != TK_OK) return rc;
+  tk_wire_mismatch* rep = (tk_wire_mismatch*)(dev + pair_bytes);
+  TK_HIP(hipMemcpyAsync(dev, pairs.data(), pairs.size() * sizeof(tk::ComparePair), hipMemcpyHostToDevice, s));
+  rc = tk::compare_impl(dev, np, blocks, rep, s);
+  if (rc != TK_OK) return rc;
+  std::vector<tk_wire_mismatch> out(np);
+  TK_HIP(hipMemcpyAsync(out.data(), rep, (size_t)np * sizeof(tk_wire_mismatch), hipMemcpyDeviceToHost, s));
+  if (hipStreamSynchronize(s) != hipSuccess) {
+    tk::set_error("tk_compare_device_batch: the compare kernel failed");
+    return TK_ERR_HIP;
+  }
+  for (int k = 0; k < np; ++k) report[index[k]] = out[k];
+  return TK_OK;
+}
+
+int tk_compare_device(const void* expected, const void* got, int64_t n_elems, int elem_bytes,
+                      tk_wire_mismatch* report, void* stream) {
+  const int32_t es = elem_bytes;
+  return tk_compare_device_batch(&expected, &got, &n_elems, &es, 1, report, stream);
+}
 
 }  // extern "C"

@@ -166,25 +166,40 @@ void clamp_block(char* dst, const char* prev, int cnt, uint8_t lo, uint8_t hi, u
   for (; i < cnt; ++i) dst[i] = (char)(clamp_u8((uint8_t)((uint8_t)prev[i] ^ flip), lo, hi) ^ flip);
 }
 
+}  // namespace
+
+// The extent of a segment of n elements of `kind` whose table entry is `start`: its unrounded
+// length by the widths its header states, or -1 if its start, its header or that length does not
+// lie inside the payload, or a width is not one the kind allows.  Reads the header only.  The host
+// decoder, tk_wire_check and (restated for the device) the decode kernel hold a segment to this.
+int64_t wire_seg_extent(int kind, int n, uint32_t start, const char* payload, int64_t payload_bytes) {
+  const int64_t off = (int64_t)start * 64;
+  const int nb = (n + kWireBlock - 1) / kWireBlock;
+  const int64_t hdr = wire_header_bytes(nb);
+  if (off > payload_bytes || hdr > payload_bytes - off) return -1;
+  const uint8_t* widths = (const uint8_t*)payload + off + wire_align(4 * (int64_t)nb, 16);
+  int64_t len = hdr;
+  const int max_w = kind == kWireI32 ? 4 : 1;
+  for (int b = 0; b < nb; ++b) {
+    if (widths[b] > max_w) return -1;
+    len += (int64_t)widths[b] * std::min(kWireBlock, n - b * kWireBlock);
+  }
+  return len > payload_bytes - off ? -1 : len;
+}
+
+namespace {
 // Decodes segment i; returns its length rounded to 64 B, or -1 if it does not lie inside the
 // payload (nothing past the payload is read, nothing outside the segment's record is written).
 int64_t decode_seg(const WireJob& j, int64_t i, const char* payload, int64_t payload_bytes) {
   const WireSegHost& sg = j.segs[i];
   uint32_t start;
   std::memcpy(&start, j.wire + 4 * i, 4);
-  const int64_t off = (int64_t)start * 64;
+  const int64_t len = wire_seg_extent(sg.kind, sg.n, start, payload, payload_bytes);
+  if (len < 0) return -1;
   const int nb = (sg.n + kWireBlock - 1) / kWireBlock;
   const int64_t hdr = wire_header_bytes(nb);
-  if (off > payload_bytes || hdr > payload_bytes - off) return -1;
-  const char* p = payload + off;
+  const char* p = payload + (int64_t)start * 64;
   const uint8_t* widths = (const uint8_t*)p + wire_align(4 * (int64_t)nb, 16);
-  int64_t len = hdr;
-  const int max_w = sg.kind == kWireI32 ? 4 : 1;
-  for (int b = 0; b < nb; ++b) {
-    if (widths[b] > max_w) return -1;
-    len += (int64_t)widths[b] * std::min(kWireBlock, sg.n - b * kWireBlock);
-  }
-  if (len > payload_bytes - off) return -1;
   const uint8_t* q = (const uint8_t*)p + hdr;
   if (sg.kind != kWireI32) {
     const uint8_t flip = sg.kind == kWireI8 ? 0x80 : 0;
@@ -403,6 +418,29 @@ int tk_wire_decode(const tk_wire_record* recs, int n_recs, const void* wire, int
   if (tk::wire_decode(&job, threads)) {
     tk::set_error("tk_wire_decode: the segment table or a segment does not lie inside the wire buffer");
     return TK_ERR_INVALID_ARG;
+  }
+  return TK_OK;
+}
+
+int tk_wire_check(const tk_wire_record* recs, int n_recs, const void* wire, int64_t wire_bytes) {
+  tk::HostPlan p;
+  const int rc = tk::host_plan(recs, n_recs, -1, &p, "tk_wire_check");
+  if (rc) return rc;
+  const int64_t n_seg = (int64_t)p.segs.size();
+  const int64_t table = tk::wire_table_bytes(n_seg);
+  if (!wire || wire_bytes < table) {
+    tk::set_error("tk_wire_check: the segment table does not lie inside the wire buffer");
+    return TK_ERR_INVALID_ARG;
+  }
+  const char* payload = (const char*)wire + table;
+  for (int64_t i = 0; i < n_seg; ++i) {
+    uint32_t start;
+    std::memcpy(&start, (const char*)wire + 4 * i, 4);
+    if (tk::wire_seg_extent(recs[p.segs[i].rec].kind, p.segs[i].n, start, payload, wire_bytes - table) < 0) {
+      tk::set_error("tk_wire_check: segment " + std::to_string(i) + " (record " + std::to_string(p.segs[i].rec) +
+                    ") does not lie inside the wire buffer or states a width its kind does not have");
+      return TK_ERR_INVALID_ARG;
+    }
   }
   return TK_OK;
 }

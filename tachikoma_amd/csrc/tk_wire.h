@@ -1,7 +1,8 @@
 // Trace wire format: int32 trace records leave the device losslessly narrowed and are widened
 // on the host; 1-byte records that are a clamp of the record before them leave as that statement
 // and are rebuilt on the host (tk_wire.cc: host decoder, thread pool and reference encoder;
-// tk_elementwise.hip: the device encoder; tk_runtime.cc: the packed capture that uses them).
+// tk_elementwise.hip: the device encoder and the device decoder that verifies and loads trace files;
+// tk_runtime.cc: the packed capture that uses them).
 //
 // A record of n int32 elements is cut into blocks of kWireBlock elements and segments of
 // kWireSegBlocks blocks (the last block / segment of a record may be short).  The coded value of
@@ -60,6 +61,27 @@ struct WireSegDev {
   int32_t n;
   int32_t kind;
 };
+// device decoder's view (tk_wire_unpack_device): a segment's destination, and a decode unit
+struct WireSegOut {
+  void* dst;  // the segment's first element in the record's buffer (device), or null
+  int32_t rec;
+  int32_t pad;
+};
+struct WireUnitDev {
+  int32_t first, stride, count;  // segments first, first + stride, ...
+  int32_t n, kind;               // elements and kind of each of them
+  int32_t pad;
+  int64_t e0;                    // the segments' first element in their records
+};
+// one pair of tk_compare_device_batch
+struct ComparePair {
+  const uint8_t* expected;
+  const uint8_t* got;
+  int64_t bytes;
+  int64_t first_blk;  // first workgroup of this pair in the launch
+  int32_t elem_bytes;
+  int32_t pad;
+};
 // host decoder's view: destinations in the trace image, any alignment
 struct WireSegHost {
   char* dst;
@@ -83,6 +105,11 @@ struct WireSegRef {
 // clamp-predicted from it).  Segments count elements, whatever their size.
 void wire_layout(const int64_t* n_elems, const int32_t* diff, int n_recs, std::vector<WireSegRef>* segs,
                  std::vector<WireUnit>* units);
+
+// Unrounded length of a segment of n elements of `kind` placed at table entry `start`, from the
+// widths its header states; -1 if start, header or length leave the payload or a width is not one
+// of the kind's (tk_wire.cc).  Reads no block payload.
+int64_t wire_seg_extent(int kind, int n, uint32_t start, const char* payload, int64_t payload_bytes);
 
 struct WireJob {
   const char* wire = nullptr;  // table | payload

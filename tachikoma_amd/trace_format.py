@@ -541,6 +541,101 @@ def unpack_trace(path_or_bytes) -> bytearray:
     return image
 
 
+@dataclass
+class CheckedTrace:
+    """A trace file of either version that passed check_trace: where its parts lie (absolute
+    offsets) and how its records are stored.  ``entries`` are in trace order; in a version-1 file
+    every entry is RAW with ``raw_off`` counted from ``records_off`` (the NDArray-list blob)."""
+    version: int
+    meta: Dict[str, Any]
+    entries: List[PackedEntry]
+    params: List[Tuple[str, Tuple[int, ...], str, int]]   # name, shape, dtype, absolute payload offset
+    params_off: int
+    params_size: int
+    records_off: int      # packed: the wire's first byte; version 1: the records blob
+    records_size: int     # packed: wire + raw; version 1: the blob
+    wire_size: int        # 0 in a version-1 file
+    size: int
+
+    @property
+    def packed(self) -> bool:
+        return self.version == PACKED_VERSION
+
+
+def _list_items(buf, off: int, size: int):
+    """(name, shape, dtype, absolute payload offset) of every array of an NDArray-list blob."""
+    base, keep = _ptr(buf)
+    out = []
+    for k, v in parse_ndarray_list(buf, off, size).items():
+        out.append((k, tuple(int(d) for d in v.shape), str(v.dtype), (v.ctypes.data - base) if v.size else off))
+    del keep
+    return out
+
+
+def check_trace(buf, records, params=None) -> CheckedTrace:
+    """Everything the host decides about a trace file before a byte of it goes to the device
+    (GraphModule.verify_trace / load_trace): ``buf`` holds the whole file.  The header and the
+    sections are parsed with every extent checked; a packed file's wire section must pass
+    tk_wire_check, which is the gate of the device decoder; and the file's record list (names,
+    dtypes, shapes, order) must equal ``records``, a list of (name, shape, dtype) -- a graph's
+    plan.records -- and likewise its params where ``params`` is given.  ValueError otherwise: a
+    truncated file, a plan or a wire table that does not hold, or a trace of another graph (or of
+    another batch size, which is another record list)."""
+    version = _header(buf)[0]
+    if version == PACKED_VERSION:
+        pf = parse_packed(buf)
+        try:
+            meta = json.loads(pf.json_text)
+        except ValueError:
+            raise ValueError("packed trace: the header json does not parse") from None
+        entries, po, ps = pf.entries, pf.params_off, pf.params_size
+        recs, n = _wire_records(entries, [0] * len(entries))
+        if n:
+            base, keep = _ptr(buf)
+            lib = _lib.load()
+            rc = lib.tk_wire_check(recs, n, ctypes.c_void_p(base + pf.wire_off), pf.wire_size)
+            del keep
+            if rc != 0:
+                raise ValueError("packed trace: " + lib.tk_last_error().decode(errors="replace"))
+        elif pf.wire_size:
+            raise ValueError("packed trace: a wire buffer without coded records")
+        records_off, records_size, wire_size = pf.wire_off, pf.wire_size + pf.raw_size, pf.wire_size
+    elif version == TRACE_VERSION:
+        _, jl, po, ps, ro, rs = _header(buf)
+        if not 56 + jl <= po <= po + ps <= ro <= ro + rs <= len(buf):
+            raise ValueError("truncated trace file")
+        try:
+            meta = json.loads(bytes(buf[56:56 + jl]).decode())
+            items = _list_items(buf, ro, rs)
+        except (struct.error, UnicodeDecodeError, KeyError, TypeError) as e:
+            raise ValueError(f"trace file: {e}") from None
+        entries = [PackedEntry(k, shape, dtype, RAW, 0, off - ro, _n_elems(shape) * np.dtype(dtype).itemsize)
+                   for k, shape, dtype, off in items]
+        if any(e.raw_off + e.raw_size > rs for e in entries):
+            raise ValueError("truncated trace file")
+        records_off, records_size, wire_size = ro, rs, 0
+    else:
+        raise ValueError(f"unsupported trace version {version}")
+    want = [(n, tuple(int(d) for d in s), str(np.dtype(d))) for n, s, d in records]
+    have = [(e.name, e.shape, e.dtype) for e in entries]
+    if have != want:
+        at = next((i for i, (a, b) in enumerate(zip(have, want)) if a != b), min(len(have), len(want)))
+        raise ValueError(f"trace is of another graph: {len(have)} records against the graph's {len(want)}, the first "
+                         f"difference at record {at} ({have[at] if at < len(have) else None} in the file, "
+                         f"{want[at] if at < len(want) else None} in the graph)")
+    try:
+        p_items = _list_items(buf, po, ps)
+    except (struct.error, UnicodeDecodeError, KeyError, TypeError) as e:
+        raise ValueError(f"trace file: {e}") from None
+    if any(off + _n_elems(shape) * np.dtype(dtype).itemsize > po + ps for _, shape, dtype, off in p_items):
+        raise ValueError("truncated trace file (params)")
+    if params is not None:
+        want_p = sorted((n, tuple(int(d) for d in s), str(np.dtype(d))) for n, s, d in params)
+        if sorted(p[:3] for p in p_items) != want_p:
+            raise ValueError("trace is of another graph: its params are not the graph's")
+    return CheckedTrace(int(version), meta, list(entries), p_items, po, ps, records_off, records_size, wire_size, len(buf))
+
+
 def packed_info(path_or_bytes) -> Dict[str, Any]:
     """Sizes and the coding plan of a packed file (``python -m tachikoma_amd.trace_format info``)."""
     pf = parse_packed(_open(path_or_bytes))

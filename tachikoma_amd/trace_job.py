@@ -26,6 +26,10 @@ its records are copied D2H (the bench's file sink, overlapped with the next batc
 CLI (one process per GPU, torch.distributed.run environment; rank 0 writes the manifest)::
 
     python -m tachikoma_amd.trace_job --model resnet50 --samples 4096 --chunk 64 --out-dir DIR [--packed]
+
+``--check`` traces nothing: it walks the rank's journal and verifies every chunk file against the
+engine on the device, record by record (:func:`check`, GraphModule.verify_trace), printing one JSON
+line per chunk; ``--verify`` keeps its meaning (re-digest the files a resumed job keeps).
 """
 from __future__ import annotations
 
@@ -221,17 +225,20 @@ class GraphModuleTracer:
         self.busy: Dict[int, "concurrent.futures.Future"] = {}
         self.digest_slots: Dict[int, "object"] = {}  # per trace image: pinned host copy of its digest
 
-    def _module(self, n: int):
+    def _module(self, n: int, captures: bool = True):
         if n not in self.modules:
-            from .contrib.graph_executor import PackedCapture, TraceCapture
             m = self.build_module(n)
             # traced runs as one replayed HIP graph: one host call per chunk, so a host that issues
             # calls late cannot starve the copies (profiles/r03r_run_modes_slow_host.txt)
             m.module.use_graph = True
-            caps = ([m.packed_capture(), PackedCapture(m.module, m._meta)] if self.packed else
-                    [m.trace_capture(), TraceCapture(m.module, m._meta)])
-            self.modules[n] = [m, caps, 0]
-        return self.modules[n]
+            self.modules[n] = [m, None, 0]
+        entry = self.modules[n]
+        if captures and entry[1] is None:  # a tracer that only checks files needs no trace images
+            from .contrib.graph_executor import PackedCapture, TraceCapture
+            m = entry[0]
+            entry[1] = ([m.packed_capture(), PackedCapture(m.module, m._meta)] if self.packed else
+                        [m.trace_capture(), TraceCapture(m.module, m._meta)])
+        return entry
 
     def __call__(self, sample_offset: int, n_samples: int, path: str):
         import torch
@@ -278,15 +285,55 @@ class GraphModuleTracer:
         self.busy[id(cap)] = fut
         return fut
 
+    def check(self, path: str):
+        """Verify one chunk file, packed or not, on the device (GraphModule.verify_trace): the
+        module is the one of the file's own ``n_samples``, and each module keeps one verifier.
+        Returns the VerifyReport; ValueError for a file that does not parse or is of another graph."""
+        with open(path, "rb") as f:
+            head = f.read(56)
+            jl = tf._header(head)[1]
+            try:
+                n = int(json.loads(f.read(jl).decode())["n_samples"])
+            except (ValueError, KeyError, TypeError):
+                raise ValueError(f"{path}: the trace header does not state n_samples") from None
+        if not 1 <= n <= 1 << 20:
+            raise ValueError(f"{path}: n_samples {n}")
+        return self._module(n, captures=False)[0].verify_trace(path)
+
     def close(self) -> None:
         """Wait for the writer, then release every module (device first, then the native module:
         GraphModule.close) while the HIP runtime is alive."""
         self.writer.shutdown(wait=True)
         for m, caps, _ in self.modules.values():
             m.close()
-            caps.clear()
+            if caps is not None:
+                caps.clear()
         self.modules.clear()
         self.digest_slots.clear()
+
+
+def check(tracer: GraphModuleTracer, out_dir: str, rank: int = 0, stem: str = "trace",
+          log: Optional[Callable[[str], None]] = None) -> List[dict]:
+    """Verify every journalled chunk file of this rank against the engine, in chunk order, following
+    each file's own version: one dict per chunk, {"chunk", "file", "ok", "n_mismatched", "first":
+    {name, op, first_index} | None, "params_equal", **stats}.  A missing or unreadable file, or one
+    that does not parse or is of another graph, is ``ok: False`` with ``"error"``."""
+    out = []
+    for index, e in sorted(Journal(journal_file(out_dir, rank, stem)).entries().items()):
+        row = {"chunk": index, "file": e.get("file")}
+        try:
+            rep = tracer.check(os.path.join(out_dir, str(e.get("file"))))
+        except (OSError, ValueError) as err:
+            row.update(ok=False, error=f"{type(err).__name__}: {err}")
+        else:
+            f = rep.first
+            row.update(ok=rep.ok, n_mismatched=len(rep.mismatches),
+                       first=None if f is None else {"name": f.name, "op": f.op, "first_index": list(f.first_index)},
+                       params_equal=rep.params_equal, **rep.stats)
+        if log:
+            log(f"rank {rank}: chunk {index} {'ok' if row['ok'] else 'FAILED'}")
+        out.append(row)
+    return out
 
 
 def main(argv=None) -> int:
@@ -299,6 +346,9 @@ def main(argv=None) -> int:
     p.add_argument("--verify", action="store_true", help="re-digest resumed chunk files")
     p.add_argument("--packed", action="store_true",
                    help="write packed (version 2) chunk files: the wire coding on disk, expanded on read")
+    p.add_argument("--check", action="store_true",
+                   help="trace nothing: verify every journalled chunk file against the engine, record by record, "
+                        "on the device; one JSON line per chunk, exit status 1 if any chunk fails")
     args = p.parse_args(argv)
     import torch
     from . import relay, zoo
@@ -320,6 +370,17 @@ def main(argv=None) -> int:
     tracer = GraphModuleTracer(build_module, proto.sample_inputs, model=proto.name, input_name=proto.input_name,
                                rank=rank, world=world, packed=args.packed)
     log = lambda s: print(f"[trace_job] {s}", file=sys.stderr, flush=True)  # noqa: E731
+    if args.check:
+        try:
+            rows = check(tracer, args.out_dir, rank, log=log)
+        finally:
+            tracer.close()
+            if world > 1:
+                import torch.distributed as dist
+                dist.destroy_process_group()
+        for row in rows:
+            print(json.dumps(dict(row, rank=rank)), flush=True)
+        return 0 if rows and all(r["ok"] for r in rows) else 1
     try:
         entries = run(tracer, args.samples, args.chunk, args.out_dir, rank, world, resume=not args.no_resume,
                       verify=args.verify, log=log, packed=args.packed)

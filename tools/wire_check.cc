@@ -1,7 +1,9 @@
 // Stand-alone check of the host wire codec (csrc/tk_wire.cc) for sanitizer builds: the cases of
 // tests/test_wire_codec.py and tests/test_wire_codec8.py restated in C++ with heap buffers of exactly the sizes the codec may
 // touch, so that AddressSanitizer sees any byte read past a wire buffer or written outside a
-// record, and UBSan any overflowing or misaligned access.  CPU only; never needs a device.
+// record, and UBSan any overflowing or misaligned access; tk_wire_check, the host gate of the device
+// decoder, is held to the decoder's verdict on every valid and damaged buffer.  CPU only; never
+// needs a device.
 //
 //   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -pthread \
 //       -I include tools/wire_check.cc tachikoma_amd/csrc/tk_wire.cc -o wire_check && ./wire_check
@@ -82,6 +84,9 @@ static int roundtrip(const Case& c, int threads, int corrupt = 0) {
   }
   const int rc = tk_wire_decode(r.data(), n, wire.get(), nb, out.get(), total, threads);
   if (!corrupt) CHECK(rc == 0 && std::memcmp(out.get(), src.get(), total) == 0);
+  // the gate of the device decoder reads the table and the headers of the same exact-size buffer
+  // and says what the decoder says
+  CHECK(tk_wire_check(r.data(), n, wire.get(), nb) == rc);
   return rc;
 }
 
@@ -122,6 +127,9 @@ static int roundtrip_any(const std::vector<AnyRec>& c, int threads, int corrupt 
   }
   const int rc = tk_wire_decode(r.data(), n, wire.get(), nb, out.get(), total, threads);
   if (!corrupt) CHECK(rc == 0 && std::memcmp(out.get(), src.get(), total) == 0);
+  // the gate of the device decoder reads the table and the headers of the same exact-size buffer
+  // and says what the decoder says
+  CHECK(tk_wire_check(r.data(), n, wire.get(), nb) == rc);
   return rc;
 }
 
