@@ -37,18 +37,11 @@ int copy_impl(const tk_tensor* x, tk_tensor* y, hipStream_t s);
 int pad_impl(const tk_tensor* x, tk_tensor* y, const tk_pad_attrs* a, hipStream_t s);
 int postops_impl(const tk_tensor* acc, const tk_tensor* sum_src, tk_tensor* y, const tk_postops_attrs* a,
                  hipStream_t s);
-int digest_impl(const void* data, int64_t nbytes, uint64_t* out, hipStream_t s);
+// tk_trace.hip: what the packed capture launches
 int host_copy_impl(const void* const* src, void* const* dst, const int64_t* bytes, int n, hipStream_t s);
 int pack_records_impl(const void* table, int nrec, int64_t blocks, void* mirror, hipStream_t s);
 int wire_encode_impl(const WireSegDev* segs, int64_t n_seg, uint32_t* cursor, void* wire, int64_t wire_bytes,
                      hipStream_t s);
-int64_t wire_scan_words(int64_t n_seg);
-int wire_pack_plan_impl(const WireSegDev* segs, int64_t n_seg, void* wire, uint64_t* scan, hipStream_t s);
-int wire_pack_place_impl(const WireSegDev* segs, int64_t n_seg, void* wire, int64_t wire_bytes, hipStream_t s);
-int wire_unpack_impl(const void* units, int64_t n_units, const void* segs, const void* wire, int64_t n_seg,
-                     int64_t wire_bytes, int mode, tk_wire_mismatch* report, int n_report, uint32_t* status,
-                     hipStream_t s);
-int compare_impl(const void* pairs, int n_pairs, int64_t blocks, tk_wire_mismatch* report, hipStream_t s);
 int ewise_impl(const tk_tensor* x, const tk_tensor* r, tk_tensor* y, const tk_ewise_attrs* a, hipStream_t s);
 int conv2d_f32_impl(const tk_tensor* x, const tk_tensor* w, tk_tensor* y, const tk_conv2d_attrs* a, hipStream_t s);
 int dense_f32_impl(const tk_tensor* x, const tk_tensor* w, tk_tensor* y, hipStream_t s);
@@ -530,9 +523,6 @@ int tk_qnn_batch_matmul(const tk_tensor* x, const tk_tensor* y, tk_tensor* out, 
                         void* workspace, void* stream) {
   return tk::batch_matmul_impl(x, y, out, attrs, workspace, tk::as_stream(stream));
 }
-int tk_digest_bytes(const void* data, int64_t nbytes, uint64_t* out_device, void* stream) {
-  return tk::digest_impl(data, nbytes, out_device, tk::as_stream(stream));
-}
 
 // ---------------------------------------------------------------- executor
 int tk_module_create(const tk_node* nodes, int n_nodes, tk_module** out) {
@@ -729,92 +719,120 @@ int tk_module_set_trace_chunks(tk_module* mod, int chunks) {
   return TK_OK;
 }
 
-// Builds the packed-capture plan for host destinations `dst`: the mirrored range, the chunks (cut
-// at node boundaries where every record below the cut is written), the device pack tables, two
-// mirrors loaded with the host image's bytes, and one graph per mirror.
-static int build_pack_plan(tk_module* mod, const std::vector<void*>& dst, PackPlan** out) {
-  auto plan = std::make_unique<PackPlan>();
-  plan->dst = dst;
-  struct Rec {
-    char* host;
-    const void* src;
-    int64_t bytes;
-    int node, out;
-    const tk_tensor* t;
-    bool wire, diff;  // coded on the wire; as the difference from the record before it
-    bool clamp;       // coded on the wire as a clamp of the record before it (1-byte)
-  };
-  // the tensor that output k of node n clips, where the node declares that output as a clip
-  auto clip_input = [](const tk::Node& n, int k) -> const void* {
-    const tk_node& d = n.desc;
-    const bool block = d.kind == TK_NODE_CONV_BLOCK || d.kind == TK_NODE_DENSE_BLOCK;
-    if ((block && d.attrs.block.has_clip) || (d.kind == TK_NODE_ADD_BLOCK && d.attrs.add_block.has_clip))
-      return k >= 1 && k == d.n_outputs - 1 ? tk::ptr(&n.out[k - 1].t) : nullptr;
-    return d.kind == TK_NODE_CLIP && k == 0 ? tk::ptr(&n.in[0].t) : nullptr;
-  };
-  std::vector<Rec> recs;
+// The steps of build_pack_plan.  A record of the plan: a node output that has a host destination.
+struct PackRecord {
+  char* host;
+  const void* src;
+  int64_t bytes;
+  int node, out;
+  const tk_tensor* t;
+  bool wire, diff;  // coded on the wire; as the difference from the record before it
+  bool clamp;       // coded on the wire as a clamp of the record before it (1-byte)
+};
+
+// the records in host order; overlapping destinations are refused
+static int collect_records(const tk_module* mod, const std::vector<void*>& dst, std::vector<PackRecord>* recs) {
   for (size_t i = 0; i < mod->nodes.size(); ++i) {
     const tk::Node& n = mod->nodes[i];
     for (int k = 0; k < n.desc.n_outputs; ++k) {
       char* h = (char*)dst[i * TK_MAX_NODE_OUTPUTS + k];
       const int64_t nb = tk::nbytes(&n.out[k].t);
-      if (h && nb > 0) recs.push_back({h, tk::ptr(&n.out[k].t), nb, (int)i, k, &n.out[k].t, false, false, false});
+      if (h && nb > 0) recs->push_back({h, tk::ptr(&n.out[k].t), nb, (int)i, k, &n.out[k].t, false, false, false});
     }
   }
-  plan->wire = mod->trace_wire && !mod->wire_forced_off;
-  if (recs.empty()) {
-    *out = nullptr;
-    return TK_OK;
-  }
-  std::sort(recs.begin(), recs.end(), [](const Rec& a, const Rec& b) { return a.host < b.host; });
-  for (size_t r = 0; r + 1 < recs.size(); ++r)
-    if (recs[r].host + recs[r].bytes > recs[r + 1].host) {
+  std::sort(recs->begin(), recs->end(), [](const PackRecord& a, const PackRecord& b) { return a.host < b.host; });
+  for (size_t r = 0; r + 1 < recs->size(); ++r)
+    if ((*recs)[r].host + (*recs)[r].bytes > (*recs)[r + 1].host) {
       tk::set_error("tk_module_run_graph: overlapping record destinations");
       return TK_ERR_INVALID_ARG;
     }
-  if (plan->wire) {
-    // int32 records are coded; one that follows (in the image) a coded record of its own shape is
-    // coded as the difference from it (every bias_add after its convolution).  A compact 1-byte
-    // record that its node declares as the clip of the record before it in the image (same dtype
-    // and shape) is coded as a clamp of that record; every other 1-byte record stays raw.
-    bool any = false;
-    for (size_t r = 0; r < recs.size(); ++r) {
-      Rec& c = recs[r];
-      const tk_tensor* a = c.t;
-      const tk_tensor* b = r ? recs[r - 1].t : nullptr;
-      const bool same_shape = b && a->ndim == b->ndim && std::equal(a->shape, a->shape + a->ndim, b->shape);
-      if (mod->wire_clamp && tk::is_int8ish(a) && tk::compact(a) && same_shape && tk::compact(b) &&
-          a->dtype.code == b->dtype.code && b->dtype.bits == 8 && b->dtype.lanes == 1 && c.src != recs[r - 1].src &&
-          clip_input(mod->nodes[c.node], c.out) == recs[r - 1].src) {
-        c.wire = c.clamp = any = true;
-        continue;
-      }
-      c.wire = tk::is_int(c.t, 32) && tk::compact(c.t) && ((uintptr_t)c.src & 3) == 0;
-      any |= c.wire;
-      if (!c.wire || r == 0 || !recs[r - 1].wire) continue;
-      c.diff = same_shape && tk::is_int(b, 32) && c.src != recs[r - 1].src;
+  return TK_OK;
+}
+
+// the tensor that output k of node n clips, where the node declares that output as a clip
+static const void* clip_input(const tk::Node& n, int k) {
+  const tk_node& d = n.desc;
+  const bool block = d.kind == TK_NODE_CONV_BLOCK || d.kind == TK_NODE_DENSE_BLOCK;
+  if ((block && d.attrs.block.has_clip) || (d.kind == TK_NODE_ADD_BLOCK && d.attrs.add_block.has_clip))
+    return k >= 1 && k == d.n_outputs - 1 ? tk::ptr(&n.out[k - 1].t) : nullptr;
+  return d.kind == TK_NODE_CLIP && k == 0 ? tk::ptr(&n.in[0].t) : nullptr;
+}
+
+// int32 records are coded; one that follows (in the image) a coded record of its own shape is
+// coded as the difference from it (every bias_add after its convolution).  A compact 1-byte
+// record that its node declares as the clip of the record before it in the image (same dtype
+// and shape) is coded as a clamp of that record; every other 1-byte record stays raw.  Returns
+// whether any record is coded.
+static bool decide_coding(const tk_module* mod, std::vector<PackRecord>& recs) {
+  bool any = false;
+  for (size_t r = 0; r < recs.size(); ++r) {
+    PackRecord& c = recs[r];
+    const tk_tensor* a = c.t;
+    const tk_tensor* b = r ? recs[r - 1].t : nullptr;
+    const bool same_shape = b && a->ndim == b->ndim && std::equal(a->shape, a->shape + a->ndim, b->shape);
+    if (mod->wire_clamp && tk::is_int8ish(a) && tk::compact(a) && same_shape && tk::compact(b) &&
+        a->dtype.code == b->dtype.code && b->dtype.bits == 8 && b->dtype.lanes == 1 && c.src != recs[r - 1].src &&
+        clip_input(mod->nodes[c.node], c.out) == recs[r - 1].src) {
+      c.wire = c.clamp = any = true;
+      continue;
     }
-    plan->wire = any;
+    c.wire = tk::is_int(c.t, 32) && tk::compact(c.t) && ((uintptr_t)c.src & 3) == 0;
+    any |= c.wire;
+    if (!c.wire || r == 0 || !recs[r - 1].wire) continue;
+    c.diff = same_shape && tk::is_int(b, 32) && c.src != recs[r - 1].src;
   }
-  plan->host_lo = recs.front().host;
-  plan->span = recs.back().host + recs.back().bytes - plan->host_lo;
+  return any;
+}
+
+// A chunk's wire tables, planned by tk::wire_plan from its coded records (`coded`: their indices in
+// `recs`): the encoder's segments (record buffers on the device), the host decoder's (image bytes),
+// the decode units and the size of a slot with every block raw.
+static int chunk_wire_tables(const std::vector<PackRecord>& recs, const std::vector<size_t>& coded,
+                             PackPlan::WireChunk* wc, std::vector<tk::WireSegDev>& wire_segs) {
+  std::vector<tk_wire_record> wrecs;  // offsets are not used here
+  for (size_t q = 0; q < coded.size(); ++q) {
+    const PackRecord& r = recs[coded[q]];
+    // a record follows its predecessor in the decode order only where that one is coded in this
+    // chunk too (a difference, or a clamp of a clamp); an earlier chunk's record, or a raw
+    // predecessor, has landed by then
+    const bool chained = (r.diff || r.clamp) && q > 0 && coded[q - 1] == coded[q] - 1;
+    const int esize = tk::elem_bytes(r.t);
+    wrecs.push_back({0, r.bytes / esize, chained, esize == 4 ? tk::kWireI32 : tk::is_int(r.t, 8) ? tk::kWireI8 : tk::kWireU8});
+  }
+  tk::WirePlan wp;
+  if (const int rc = tk::wire_plan(wrecs.data(), (int)wrecs.size(), -1, "tk_module_run_graph", &wp)) return rc;
+  wc->units = std::move(wp.units);
+  wc->seg_off = (int64_t)wire_segs.size();
+  wc->bound = wp.bound;
+  for (const tk::WireSegRef& sr : wp.segs) {
+    const PackRecord& r = recs[coded[sr.rec]];
+    // a differenced record's predecessor is the record before it in the image (this chunk's
+    // or, for the chunk's first record, an earlier chunk's: decoded before this one)
+    const PackRecord* pv = r.diff || r.clamp ? &recs[coded[sr.rec] - 1] : nullptr;
+    const int kind = wrecs[sr.rec].kind;
+    const tk::WireSegAddr dev = tk::wire_seg_addr(sr, kind, r.src, pv ? pv->src : nullptr);
+    const tk::WireSegAddr img = tk::wire_seg_addr(sr, kind, r.host, pv ? pv->host : nullptr);
+    wire_segs.push_back({dev.at, dev.prev, sr.n, kind});
+    wc->segs.push_back({img.at, img.prev, sr.n, kind});
+  }
+  for (size_t q : coded) wc->coded_bytes += recs[q].bytes;
+  return TK_OK;
+}
+
+// The chunks, cut at node boundaries where every record below the cut is written, with the pack
+// table and, on the wire, each chunk's raw ranges and wire tables.
+static int cut_chunks(const tk_module* mod, const std::vector<PackRecord>& recs, PackPlan* plan,
+                      std::vector<PackRecHost>& table, std::vector<tk::WireSegDev>& wire_segs) {
   // after node i, every record below complete_upto[i] (host order) is written
   const int nn = (int)mod->nodes.size();
   std::vector<int64_t> complete_upto(nn);
-  {
-    int r = 0;
-    int last_node = -1;  // max producer node among records [0, r)
-    std::vector<int> prefix_max(recs.size());
-    for (size_t q = 0; q < recs.size(); ++q) prefix_max[q] = std::max(q ? prefix_max[q - 1] : -1, recs[q].node);
-    for (int i = 0; i < nn; ++i) {
-      while (r < (int)recs.size() && prefix_max[r] <= i) ++r;
-      complete_upto[i] = r == (int)recs.size() ? plan->span : recs[r].host - plan->host_lo;
-      (void)last_node;
-    }
+  std::vector<int> prefix_max(recs.size());  // max producer node among records [0, q]
+  for (size_t q = 0; q < recs.size(); ++q) prefix_max[q] = std::max(q ? prefix_max[q - 1] : -1, recs[q].node);
+  for (int i = 0, r = 0; i < nn; ++i) {
+    while (r < (int)recs.size() && prefix_max[r] <= i) ++r;
+    complete_upto[i] = r == (int)recs.size() ? plan->span : recs[r].host - plan->host_lo;
   }
   const int64_t target = std::max<int64_t>(1, (plan->span + mod->pack_chunks - 1) / mod->pack_chunks);
-  std::vector<PackRecHost> table;
-  std::vector<tk::WireSegDev> wire_segs;
   int64_t cut = 0;
   size_t next_rec = 0;
   for (int i = 0; i < nn; ++i) {
@@ -824,18 +842,13 @@ static int build_pack_plan(tk_module* mod, const std::vector<void*>& dst, PackPl
     PackPlan::Chunk c{i, cut, upto - cut, (int64_t)table.size(), 0, 0};
     int64_t blocks = 0;
     PackPlan::WireChunk wc;
-    std::vector<int64_t> w_elems;
-    std::vector<int32_t> w_diff;
-    std::vector<size_t> w_rec;
+    std::vector<size_t> w_rec;  // the chunk's coded records
     bool in_run = false;  // the previous record of this chunk was not coded
     while (next_rec < recs.size() && recs[next_rec].host - plan->host_lo < upto) {
-      const Rec& rc = recs[next_rec++];
+      const PackRecord& rc = recs[next_rec++];
       const int64_t off = rc.host - plan->host_lo;
       if (rc.wire) {
-        // a clamp-coded record follows its predecessor in the decode order only where that one is
-        // coded in this chunk too (a clamp of a clamp); a raw predecessor has landed by then
-        const bool chained = rc.diff || (rc.clamp && !w_rec.empty() && w_rec.back() == next_rec - 2);
-        w_elems.push_back(rc.bytes / tk::elem_bytes(rc.t)), w_diff.push_back(chained), w_rec.push_back(next_rec - 1);
+        w_rec.push_back(next_rec - 1);
         in_run = false;
         continue;
       }
@@ -854,38 +867,27 @@ static int build_pack_plan(tk_module* mod, const std::vector<void*>& dst, PackPl
     plan->chunks.push_back(c);
     cut = upto;
     if (!plan->wire) continue;
-    if (!w_rec.empty()) {
-      std::vector<tk::WireSegRef> refs;
-      tk::wire_layout(w_elems.data(), w_diff.data(), (int)w_rec.size(), &refs, &wc.units);
-      wc.seg_off = (int64_t)wire_segs.size();
-      wc.bound = tk::wire_table_bytes((int64_t)refs.size());
-      for (const tk::WireSegRef& sr : refs) {
-        const Rec& rc = recs[w_rec[sr.rec]];
-        // a differenced record's predecessor is the record before it in the image (this chunk's
-        // or, for the chunk's first record, an earlier chunk's: decoded before this one)
-        const Rec* pv = rc.diff || rc.clamp ? &recs[w_rec[sr.rec] - 1] : nullptr;
-        const int esize = tk::elem_bytes(rc.t);
-        const int kind = esize == 4 ? tk::kWireI32 : tk::is_int(rc.t, 8) ? tk::kWireI8 : tk::kWireU8;
-        const int64_t e0 = esize * sr.e0;
-        wire_segs.push_back({(const char*)rc.src + e0, pv ? (const char*)pv->src + e0 : nullptr, sr.n, kind});
-        wc.segs.push_back({rc.host + e0, pv ? pv->host + e0 : nullptr, sr.n, kind});
-        wc.bound += tk::wire_seg_bound(sr.n, esize);
-      }
-      for (size_t q : w_rec) wc.coded_bytes += recs[q].bytes;
-    }
+    if (!w_rec.empty())
+      if (const int rc = chunk_wire_tables(recs, w_rec, &wc, wire_segs)) return rc;
     plan->wchunks.push_back(std::move(wc));
   }
   if (cut != plan->span || next_rec != recs.size()) {
     tk::set_error("tk_module_run_graph: pack plan does not cover every record");
     return TK_ERR_INVALID_ARG;
   }
+  return TK_OK;
+}
+
+// The device pack table, two mirrors and their events; on the wire also the device segment table,
+// a ring of pinned slots each large enough for any chunk with every block raw, a cursor per slot,
+// the decode calls of every (chunk, slot) pair and the module's streams.
+static int alloc_pack_resources(tk_module* mod, PackPlan* plan, const std::vector<PackRecHost>& table,
+                                const std::vector<tk::WireSegDev>& wire_segs) {
   if (!table.empty()) {
     TK_HIP(hipMalloc(&plan->table, table.size() * sizeof(PackRecHost)));
     TK_HIP(hipMemcpy(plan->table, table.data(), table.size() * sizeof(PackRecHost), hipMemcpyHostToDevice));
   }
   if (plan->wire) {
-    // the device segment table, a ring of pinned slots each large enough for any chunk with every
-    // block raw, a cursor per slot, and the decode calls of every (chunk, slot) pair
     TK_HIP(hipMalloc(&plan->wire_segs, wire_segs.size() * sizeof(tk::WireSegDev)));
     TK_HIP(hipMemcpy(plan->wire_segs, wire_segs.data(), wire_segs.size() * sizeof(tk::WireSegDev), hipMemcpyHostToDevice));
     int64_t slot_bytes = 0;
@@ -929,10 +931,15 @@ static int build_pack_plan(tk_module* mod, const std::vector<void*>& dst, PackPl
     for (auto& e : plan->ev[m]) TK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   }
   if (!mod->cap_s) TK_HIP(hipStreamCreateWithFlags(&mod->cap_s, hipStreamNonBlocking));
-  // one graph per chunk: the nodes up to the chunk's last producer and its pack kernel (a tail
-  // graph holds the nodes after the last chunk).  The copy of chunk c waits on an event recorded
-  // between graph launches c and c + 1; external event-record nodes inside one graph would do the
-  // same in one launch, but torch's bundled HIP runtime (7.0) refuses them in capture.
+  return TK_OK;
+}
+
+// One graph per chunk and mirror: the nodes up to the chunk's last producer and its pack kernel (a
+// tail graph holds the nodes after the last chunk).  The copy of chunk c waits on an event recorded
+// between graph launches c and c + 1; external event-record nodes inside one graph would do the
+// same in one launch, but torch's bundled HIP runtime (7.0) refuses them in capture.
+static int capture_chunk_graphs(tk_module* mod, PackPlan* plan) {
+  const int nn = (int)mod->nodes.size();
   const int nseg = (int)plan->chunks.size() + (plan->chunks.back().after_node < nn - 1 ? 1 : 0);
   for (int m = 0; m < 2; ++m) {
     hipStream_t qs = mod->cap_s;
@@ -972,6 +979,29 @@ static int build_pack_plan(tk_module* mod, const std::vector<void*>& dst, PackPl
       plan->ge[m].push_back(ge);
     }
   }
+  return TK_OK;
+}
+
+// Builds the packed-capture plan for host destinations `dst`: the mirrored range, the chunks (cut
+// at node boundaries where every record below the cut is written), the device pack tables, two
+// mirrors loaded with the host image's bytes, and one graph per chunk and mirror.
+static int build_pack_plan(tk_module* mod, const std::vector<void*>& dst, PackPlan** out) {
+  auto plan = std::make_unique<PackPlan>();
+  plan->dst = dst;
+  std::vector<PackRecord> recs;
+  if (const int rc = collect_records(mod, dst, &recs)) return rc;
+  if (recs.empty()) {
+    *out = nullptr;
+    return TK_OK;
+  }
+  plan->wire = mod->trace_wire && !mod->wire_forced_off && decide_coding(mod, recs);
+  plan->host_lo = recs.front().host;
+  plan->span = recs.back().host + recs.back().bytes - plan->host_lo;
+  std::vector<PackRecHost> table;
+  std::vector<tk::WireSegDev> wire_segs;
+  if (const int rc = cut_chunks(mod, recs, plan.get(), table, wire_segs)) return rc;
+  if (const int rc = alloc_pack_resources(mod, plan.get(), table, wire_segs)) return rc;
+  if (const int rc = capture_chunk_graphs(mod, plan.get())) return rc;
   *out = plan.release();
   return TK_OK;
 }
@@ -1505,271 +1535,6 @@ int tk_module_tune(tk_module* mod, void* stream, int max_candidates, int reps, i
     (void)hipFree(flush);
   }
   return rc;
-}
-
-int tk_wire_encode_device(const tk_wire_record* recs, int n_recs, const void* const* src, void* wire,
-                          int64_t wire_cap, void* stream) {
-  const int64_t bound = tk_wire_bound(recs, n_recs);
-  if (bound < 0) return (int)bound;
-  if (!src || !wire || wire_cap < bound) {
-    tk::set_error("tk_wire_encode_device: the wire buffer is smaller than tk_wire_bound");
-    return TK_ERR_INVALID_ARG;
-  }
-  std::vector<int64_t> n(n_recs);
-  std::vector<int32_t> d(n_recs);
-  for (int i = 0; i < n_recs; ++i) n[i] = recs[i].n_elems, d[i] = recs[i].diff != 0;
-  std::vector<tk::WireSegRef> refs;
-  std::vector<tk::WireUnit> units;
-  tk::wire_layout(n.data(), d.data(), n_recs, &refs, &units);
-  std::vector<tk::WireSegDev> segs;
-  for (const tk::WireSegRef& r : refs) {
-    const int64_t e0 = tk::wire_elem_bytes(recs[r.rec].kind) * r.e0;
-    segs.push_back({(const char*)src[r.rec] + e0, recs[r.rec].diff ? (const char*)src[r.rec - 1] + e0 : nullptr, r.n,
-                    recs[r.rec].kind});
-  }
-  hipStream_t s = tk::as_stream(stream);
-  void* dev = nullptr;
-  TK_HIP(hipMalloc(&dev, segs.size() * sizeof(tk::WireSegDev) + 64));
-  uint32_t* cursor = (uint32_t*)((char*)dev + segs.size() * sizeof(tk::WireSegDev));
-  int rc = TK_OK;
-  if (hipMemcpyAsync(dev, segs.data(), segs.size() * sizeof(tk::WireSegDev), hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipMemsetAsync(cursor, 0, sizeof(uint32_t), s) != hipSuccess) {
-    tk::set_error("tk_wire_encode_device: loading the segment table failed");
-    rc = TK_ERR_HIP;
-  }
-  if (rc == TK_OK) rc = tk::wire_encode_impl((const tk::WireSegDev*)dev, (int64_t)segs.size(), cursor, wire, bound, s);
-  if (hipStreamSynchronize(s) != hipSuccess && rc == TK_OK) {
-    tk::set_error("tk_wire_encode_device: the encode kernel failed");
-    rc = TK_ERR_HIP;
-  }
-  (void)hipFree(dev);
-  return rc;
-}
-
-namespace {
-// Device scratch of tk_wire_pack_device (the segment list and the scan's levels): kept between
-// calls and only ever grown, because a trace job packs every chunk and hipFree would wait for the
-// previous chunk's copy.  One call at a time uses it.
-struct PackScratch {
-  std::mutex mu;
-  void* dev = nullptr;
-  int64_t bytes = 0;
-  int device = -1;
-};
-PackScratch g_pack_scratch;
-}  // namespace
-
-int64_t tk_wire_pack_device(const tk_wire_record* recs, int n_recs, const void* const* src, void* wire,
-                            int64_t wire_cap, void* stream) {
-  const int64_t bound = tk_wire_bound(recs, n_recs);
-  if (bound < 0) return bound;
-  if (!src || !wire || ((uintptr_t)wire & 63) != 0 || wire_cap < bound) {
-    tk::set_error("tk_wire_pack_device: the wire buffer is not 64-byte aligned or smaller than tk_wire_bound");
-    return TK_ERR_INVALID_ARG;
-  }
-  std::vector<int64_t> n(n_recs);
-  std::vector<int32_t> d(n_recs);
-  for (int i = 0; i < n_recs; ++i) n[i] = recs[i].n_elems, d[i] = recs[i].diff != 0;
-  std::vector<tk::WireSegRef> refs;
-  std::vector<tk::WireUnit> units;
-  tk::wire_layout(n.data(), d.data(), n_recs, &refs, &units);
-  if (refs.size() >= ((size_t)1 << 31)) {
-    tk::set_error("tk_wire_pack_device: too many segments");
-    return TK_ERR_UNSUPPORTED;
-  }
-  std::vector<tk::WireSegDev> segs;
-  segs.reserve(refs.size());
-  for (const tk::WireSegRef& r : refs) {
-    const int64_t e0 = tk::wire_elem_bytes(recs[r.rec].kind) * r.e0;
-    segs.push_back({(const char*)src[r.rec] + e0, recs[r.rec].diff ? (const char*)src[r.rec - 1] + e0 : nullptr, r.n,
-                    recs[r.rec].kind});
-  }
-  const int64_t n_seg = (int64_t)segs.size();
-  const int64_t table = tk::wire_table_bytes(n_seg);
-  const int64_t seg_bytes = tk::wire_align(n_seg * (int64_t)sizeof(tk::WireSegDev), 64);
-  const int64_t words = tk::wire_scan_words(n_seg);
-  hipStream_t s = tk::as_stream(stream);
-  std::lock_guard<std::mutex> lock(g_pack_scratch.mu);
-  int device = 0;
-  TK_HIP(hipGetDevice(&device));
-  if (g_pack_scratch.device != device || g_pack_scratch.bytes < seg_bytes + 8 * words) {
-    if (g_pack_scratch.dev) (void)hipFree(g_pack_scratch.dev);
-    g_pack_scratch.dev = nullptr, g_pack_scratch.bytes = 0;
-    TK_HIP(hipMalloc(&g_pack_scratch.dev, (size_t)(seg_bytes + 8 * words)));
-    g_pack_scratch.bytes = seg_bytes + 8 * words, g_pack_scratch.device = device;
-  }
-  const tk::WireSegDev* dev_segs = (const tk::WireSegDev*)g_pack_scratch.dev;
-  uint64_t* scan = (uint64_t*)((char*)g_pack_scratch.dev + seg_bytes);
-  TK_HIP(hipMemcpyAsync(g_pack_scratch.dev, segs.data(), segs.size() * sizeof(tk::WireSegDev), hipMemcpyHostToDevice, s));
-  int rc = tk::wire_pack_plan_impl(dev_segs, n_seg, wire, scan, s);
-  if (rc != TK_OK) return rc;
-  uint64_t total = 0;  // payload units; the copy returns once the value is here
-  TK_HIP(hipMemcpyAsync(&total, scan + words - 1, sizeof(total), hipMemcpyDeviceToHost, s));
-  TK_HIP(hipStreamSynchronize(s));
-  if (total > 0xFFFFFFF0ull) {
-    tk::set_error("tk_wire_pack_device: the packed records do not fit the format's 32-bit segment starts");
-    return TK_ERR_UNSUPPORTED;
-  }
-  const int64_t used = table + 64 * (int64_t)total;
-  if (used > bound) {
-    tk::set_error("tk_wire_pack_device: the segment sizes exceed tk_wire_bound");
-    return TK_ERR_HIP;
-  }
-  rc = tk::wire_pack_place_impl(dev_segs, n_seg, wire, used, s);
-  if (rc != TK_OK) return rc;
-  if (hipStreamSynchronize(s) != hipSuccess) {
-    tk::set_error("tk_wire_pack_device: the place kernel failed");
-    return TK_ERR_HIP;
-  }
-  return used;
-}
-
-int tk_wire_pack_tile(void) { return tk::kWireScanTile; }
-
-namespace {
-// Device scratch of tk_wire_unpack_device / tk_compare_device_batch (unit, segment or pair lists,
-// the report and the status word): kept between calls and only ever grown, as the packer's.
-PackScratch g_unpack_scratch;
-
-int unpack_scratch(int64_t bytes, char** out) {
-  int device = 0;
-  TK_HIP(hipGetDevice(&device));
-  if (g_unpack_scratch.device != device || g_unpack_scratch.bytes < bytes) {
-    if (g_unpack_scratch.dev) (void)hipFree(g_unpack_scratch.dev);
-    g_unpack_scratch.dev = nullptr, g_unpack_scratch.bytes = 0;
-    TK_HIP(hipMalloc(&g_unpack_scratch.dev, (size_t)bytes));
-    g_unpack_scratch.bytes = bytes, g_unpack_scratch.device = device;
-  }
-  *out = (char*)g_unpack_scratch.dev;
-  return TK_OK;
-}
-}  // namespace
-
-int tk_wire_unpack_device(const tk_wire_record* recs, int n_recs, const void* wire, int64_t wire_bytes,
-                          void* const* dst, int mode, tk_wire_mismatch* report, void* stream) {
-  const int64_t bound = tk_wire_bound(recs, n_recs);  // host_plan's rules
-  if (bound < 0) return (int)bound;
-  const bool compare = mode == TK_WIRE_UNPACK_COMPARE;
-  if (!wire || !dst || ((uintptr_t)wire & 63) != 0 || (mode != TK_WIRE_UNPACK_STORE && !compare) ||
-      (compare && !report)) {
-    tk::set_error("tk_wire_unpack_device: null argument, unknown mode or a wire buffer that is not 64-byte aligned");
-    return TK_ERR_INVALID_ARG;
-  }
-  for (int i = 0; i < n_recs; ++i)
-    if (recs[i].kind == tk::kWireI32 && ((uintptr_t)dst[i] & 3) != 0) {
-      tk::set_error("tk_wire_unpack_device: the buffer of int32 record " + std::to_string(i) + " is not 4-byte aligned");
-      return TK_ERR_INVALID_ARG;
-    }
-  std::vector<int64_t> n(n_recs);
-  std::vector<int32_t> d(n_recs);
-  for (int i = 0; i < n_recs; ++i) n[i] = recs[i].n_elems, d[i] = recs[i].diff != 0;
-  std::vector<tk::WireSegRef> refs;
-  std::vector<tk::WireUnit> units;
-  tk::wire_layout(n.data(), d.data(), n_recs, &refs, &units);
-  const int64_t n_seg = (int64_t)refs.size(), n_units = (int64_t)units.size();
-  if (n_seg >= ((int64_t)1 << 31)) {
-    tk::set_error("tk_wire_unpack_device: too many segments");
-    return TK_ERR_UNSUPPORTED;
-  }
-  if (wire_bytes < tk::wire_table_bytes(n_seg)) {
-    tk::set_error("tk_wire_unpack_device: the segment table does not lie inside the wire buffer");
-    return TK_ERR_INVALID_ARG;
-  }
-  std::vector<tk::WireSegOut> segs(refs.size());
-  for (size_t i = 0; i < refs.size(); ++i) {
-    const tk::WireSegRef& r = refs[i];
-    char* base = (char*)dst[r.rec];
-    segs[i] = {base ? base + tk::wire_elem_bytes(recs[r.rec].kind) * r.e0 : nullptr, r.rec, 0};
-  }
-  std::vector<tk::WireUnitDev> udev(units.size());
-  for (size_t u = 0; u < units.size(); ++u) {
-    const tk::WireSegRef& r = refs[units[u].first];
-    udev[u] = {units[u].first, units[u].stride, units[u].count, r.n, recs[r.rec].kind, 0, r.e0};
-  }
-  const int64_t seg_bytes = tk::wire_align(n_seg * (int64_t)sizeof(tk::WireSegOut), 64);
-  const int64_t unit_bytes = tk::wire_align(n_units * (int64_t)sizeof(tk::WireUnitDev), 64);
-  const int64_t rep_bytes = tk::wire_align((int64_t)n_recs * (int64_t)sizeof(tk_wire_mismatch), 64);
-  hipStream_t s = tk::as_stream(stream);
-  std::lock_guard<std::mutex> lock(g_unpack_scratch.mu);
-  char* dev = nullptr;
-  int rc = unpack_scratch(seg_bytes + unit_bytes + rep_bytes + 64, &dev);
-  if (rc != TK_OK) return rc;
-  tk_wire_mismatch* rep = (tk_wire_mismatch*)(dev + seg_bytes + unit_bytes);
-  uint32_t* status = (uint32_t*)(dev + seg_bytes + unit_bytes + rep_bytes);
-  TK_HIP(hipMemcpyAsync(dev, segs.data(), segs.size() * sizeof(tk::WireSegOut), hipMemcpyHostToDevice, s));
-  TK_HIP(hipMemcpyAsync(dev + seg_bytes, udev.data(), udev.size() * sizeof(tk::WireUnitDev), hipMemcpyHostToDevice, s));
-  TK_HIP(hipMemsetAsync(status, 0, sizeof(uint32_t), s));
-  rc = tk::wire_unpack_impl(dev + seg_bytes, n_units, dev, wire, n_seg, wire_bytes, mode, rep, n_recs, status, s);
-  if (rc != TK_OK) return rc;
-  uint32_t bad = 0;
-  if (compare) TK_HIP(hipMemcpyAsync(report, rep, (size_t)n_recs * sizeof(tk_wire_mismatch), hipMemcpyDeviceToHost, s));
-  TK_HIP(hipMemcpyAsync(&bad, status, sizeof(bad), hipMemcpyDeviceToHost, s));
-  if (hipStreamSynchronize(s) != hipSuccess) {
-    tk::set_error("tk_wire_unpack_device: the decode kernel failed");
-    return TK_ERR_HIP;
-  }
-  if (bad) {
-    tk::set_error("tk_wire_unpack_device: a segment does not lie inside the wire buffer or states a width its kind "
-                  "does not have (was the buffer checked with tk_wire_check?)");
-    return TK_ERR_INVALID_ARG;
-  }
-  return TK_OK;
-}
-
-int tk_compare_device_batch(const void* const* expected, const void* const* got, const int64_t* n_elems,
-                            const int32_t* elem_bytes, int n, tk_wire_mismatch* report, void* stream) {
-  if (!expected || !got || !n_elems || !elem_bytes || !report || n < 1) {
-    tk::set_error("tk_compare_device_batch: null argument or no pairs");
-    return TK_ERR_INVALID_ARG;
-  }
-  std::vector<tk::ComparePair> pairs;
-  std::vector<int> index;  // pair of the launch -> pair of the call (empty pairs are not launched)
-  int64_t blocks = 0;
-  for (int i = 0; i < n; ++i) {
-    const int es = elem_bytes[i];
-    if ((es != 1 && es != 2 && es != 4 && es != 8) || n_elems[i] < 0 || n_elems[i] > ((int64_t)1 << 40) ||
-        (n_elems[i] > 0 && (!expected[i] || !got[i]))) {
-      tk::set_error("tk_compare_device_batch: pair " + std::to_string(i) +
-                    " has a null buffer, a negative count or an element size other than 1, 2, 4, 8");
-      return TK_ERR_INVALID_ARG;
-    }
-    report[i].mismatches = 0, report[i].first = ~(uint64_t)0;
-    if (n_elems[i] == 0) continue;
-    const int64_t bytes = n_elems[i] * es;
-    pairs.push_back({(const uint8_t*)expected[i], (const uint8_t*)got[i], bytes, blocks, es, 0});
-    index.push_back(i);
-    blocks += (bytes + 4095) / 4096;
-  }
-  if (pairs.empty()) return TK_OK;
-  if (blocks >= ((int64_t)1 << 31)) {
-    tk::set_error("tk_compare_device_batch: too much to compare in one launch");
-    return TK_ERR_UNSUPPORTED;
-  }
-  const int np = (int)pairs.size();
-  const int64_t pair_bytes = tk::wire_align(np * (int64_t)sizeof(tk::ComparePair), 64);
-  hipStream_t s = tk::as_stream(stream);
-  std::lock_guard<std::mutex> lock(g_unpack_scratch.mu);
-  char* dev = nullptr;
-  int rc = unpack_scratch(pair_bytes + np * (int64_t)sizeof(tk_wire_mismatch), &dev);
-  if (rc != TK_OK) return rc;
-  tk_wire_mismatch* rep = (tk_wire_mismatch*)(dev + pair_bytes);
-  TK_HIP(hipMemcpyAsync(dev, pairs.data(), pairs.size() * sizeof(tk::ComparePair), hipMemcpyHostToDevice, s));
-  rc = tk::compare_impl(dev, np, blocks, rep, s);
-  if (rc != TK_OK) return rc;
-  std::vector<tk_wire_mismatch> out(np);
-  TK_HIP(hipMemcpyAsync(out.data(), rep, (size_t)np * sizeof(tk_wire_mismatch), hipMemcpyDeviceToHost, s));
-  if (hipStreamSynchronize(s) != hipSuccess) {
-    tk::set_error("tk_compare_device_batch: the compare kernel failed");
-    return TK_ERR_HIP;
-  }
-  for (int k = 0; k < np; ++k) report[index[k]] = out[k];
-  return TK_OK;
-}
-
-int tk_compare_device(const void* expected, const void* got, int64_t n_elems, int elem_bytes,
-                      tk_wire_mismatch* report, void* stream) {
-  const int32_t es = elem_bytes;
-  return tk_compare_device_batch(&expected, &got, &n_elems, &es, 1, report, stream);
 }
 
 }  // extern "C"

@@ -1,6 +1,8 @@
-// Host side of the trace wire format (tk_wire.h): the decoder that widens a wire buffer into the
-// trace image (and rebuilds clamp-predicted 1-byte records from the image bytes before them) on a fixed thread pool, and a reference encoder so the decoder is testable without
-// a device.  Plain C++ (no HIP): also compiled alone into the sanitizer check of tools/wire_check.cc.
+// Host side of the trace wire format (tk_wire.h): the planner every encoder and decoder lays its
+// records out with, the decoder that widens a wire buffer into the trace image (and rebuilds
+// clamp-predicted 1-byte records from the image bytes before them) on a fixed thread pool, and a
+// reference encoder so the decoder is testable without a device.  Plain C++ (no HIP): also
+// compiled alone into the sanitizer check of tools/wire_check.cc.
 #include "tk_wire.h"
 
 #include <sched.h>
@@ -15,28 +17,53 @@
 #include <string>
 #include <thread>
 
-#include "../../include/tachikoma.h"
-
 namespace tk {
 void set_error(const std::string& msg);
 
-void wire_layout(const int64_t* n_elems, const int32_t* diff, int n_recs, std::vector<WireSegRef>* segs,
-                 std::vector<WireUnit>* units) {
-  segs->clear();
-  units->clear();
+int wire_plan(const tk_wire_record* recs, int n_recs, int64_t image_bytes, const char* who, WirePlan* p) {
+  if (!recs || n_recs < 1) {
+    set_error(std::string(who) + ": no records");
+    return TK_ERR_INVALID_ARG;
+  }
+  int64_t n_seg = 0;
+  for (int i = 0; i < n_recs; ++i) {
+    const int kind = recs[i].kind;
+    const int64_t esize = wire_elem_bytes(kind);
+    const bool inside = kind >= kWireI32 && kind <= kWireU8 && recs[i].offset >= 0 && recs[i].n_elems >= 1 &&
+                        recs[i].n_elems <= ((int64_t)1 << 40) &&
+                        (image_bytes < 0 ||
+                         (recs[i].offset <= image_bytes && esize * recs[i].n_elems <= image_bytes - recs[i].offset));
+    if (!inside || (recs[i].diff && (i == 0 || recs[i - 1].n_elems != recs[i].n_elems || recs[i - 1].kind != kind))) {
+      set_error(std::string(who) + ": record " + std::to_string(i) +
+                " is of no known kind, lies outside the image or follows (diff) a record of another size or kind");
+      return TK_ERR_INVALID_ARG;
+    }
+    n_seg += (recs[i].n_elems + kWireSegElems - 1) / kWireSegElems;
+  }
+  if (n_seg >= ((int64_t)1 << 31)) {  // segment indices are 32-bit, on the host and on the device
+    set_error(std::string(who) + ": too many segments");
+    return TK_ERR_UNSUPPORTED;
+  }
+  p->segs.clear(), p->units.clear();
+  p->segs.reserve((size_t)n_seg);
+  p->bound = wire_table_bytes(n_seg);
   int r = 0;
   while (r < n_recs) {
     int k = 1;  // records r .. r + k - 1 form a chain
-    while (r + k < n_recs && diff[r + k]) ++k;
-    const int64_t n = n_elems[r];
+    while (r + k < n_recs && recs[r + k].diff) ++k;
+    const int64_t n = recs[r].n_elems;
     const int64_t S = (n + kWireSegElems - 1) / kWireSegElems;
-    const int64_t first = (int64_t)segs->size();
+    const int64_t first = (int64_t)p->segs.size();
     for (int m = 0; m < k; ++m)
-      for (int64_t j = 0; j < S; ++j)
-        segs->push_back({r + m, (int32_t)std::min<int64_t>(kWireSegElems, n - j * kWireSegElems), j * kWireSegElems});
-    for (int64_t j = 0; j < S; ++j) units->push_back({(int32_t)(first + j), (int32_t)S, k});
+      for (int64_t j = 0; j < S; ++j) {
+        const int32_t sn = (int32_t)std::min<int64_t>(kWireSegElems, n - j * kWireSegElems);
+        p->segs.push_back({r + m, sn, j * kWireSegElems});
+        p->bound += wire_seg_bound(sn, wire_elem_bytes(recs[r].kind));
+      }
+    for (int64_t j = 0; j < S; ++j) p->units.push_back({(int32_t)(first + j), (int32_t)S, k});
     r += k;
   }
+  return TK_OK;
 }
 
 // ---------------------------------------------------------------- thread pool
@@ -316,55 +343,21 @@ int64_t encode_seg8(const char* src, const char* prev, int n, int kind, char* ou
   }
   return (char*)q - out;
 }
-
-struct HostPlan {
-  std::vector<WireSegRef> segs;
-  std::vector<WireUnit> units;
-  int64_t bound = 0;
-};
-int host_plan(const tk_wire_record* recs, int n_recs, int64_t image_bytes, HostPlan* p, const char* who) {
-  if (!recs || n_recs < 1) {
-    set_error(std::string(who) + ": no records");
-    return TK_ERR_INVALID_ARG;
-  }
-  std::vector<int64_t> n(n_recs);
-  std::vector<int32_t> d(n_recs);
-  for (int i = 0; i < n_recs; ++i) {
-    n[i] = recs[i].n_elems;
-    d[i] = recs[i].diff != 0;
-    const int kind = recs[i].kind;
-    const int64_t esize = wire_elem_bytes(kind);
-    const bool inside = kind >= kWireI32 && kind <= kWireU8 && recs[i].offset >= 0 && recs[i].n_elems >= 1 &&
-                        recs[i].n_elems <= ((int64_t)1 << 40) &&
-                        (image_bytes < 0 ||
-                         (recs[i].offset <= image_bytes && esize * recs[i].n_elems <= image_bytes - recs[i].offset));
-    if (!inside || (d[i] && (i == 0 || recs[i - 1].n_elems != recs[i].n_elems || recs[i - 1].kind != kind))) {
-      set_error(std::string(who) + ": record " + std::to_string(i) +
-                " is of no known kind, lies outside the image or follows (diff) a record of another size or kind");
-      return TK_ERR_INVALID_ARG;
-    }
-  }
-  wire_layout(n.data(), d.data(), n_recs, &p->segs, &p->units);
-  p->bound = wire_table_bytes((int64_t)p->segs.size());
-  for (const WireSegRef& s : p->segs) p->bound += wire_seg_bound(s.n, wire_elem_bytes(recs[s.rec].kind));
-  return TK_OK;
-}
 }  // namespace
 }  // namespace tk
 
 extern "C" {
 
 int64_t tk_wire_bound(const tk_wire_record* recs, int n_recs) {
-  tk::HostPlan p;
-  const int rc = tk::host_plan(recs, n_recs, -1, &p, "tk_wire_bound");
+  tk::WirePlan p;
+  const int rc = tk::wire_plan(recs, n_recs, -1, "tk_wire_bound", &p);
   return rc ? rc : p.bound;
 }
 
 int64_t tk_wire_encode_host(const tk_wire_record* recs, int n_recs, const void* image, int64_t image_bytes,
                             void* wire, int64_t wire_cap) {
-  tk::HostPlan p;
-  const int rc = tk::host_plan(recs, n_recs, image_bytes, &p, "tk_wire_encode_host");
-  if (rc) return rc;
+  tk::WirePlan p;
+  if (const int rc = tk::wire_plan(recs, n_recs, image_bytes, "tk_wire_encode_host", &p)) return rc;
   if (!image || !wire || wire_cap < p.bound) {
     tk::set_error("tk_wire_encode_host: the wire buffer is smaller than tk_wire_bound");
     return TK_ERR_INVALID_ARG;
@@ -376,13 +369,13 @@ int64_t tk_wire_encode_host(const tk_wire_record* recs, int n_recs, const void* 
   for (size_t i = 0; i < p.segs.size(); ++i) {
     const tk::WireSegRef& s = p.segs[i];
     const int kind = recs[s.rec].kind;
-    const int64_t e0 = tk::wire_elem_bytes(kind) * s.e0;
-    const char* src = (const char*)image + recs[s.rec].offset + e0;
-    const char* prev = recs[s.rec].diff ? (const char*)image + recs[s.rec - 1].offset + e0 : nullptr;
+    const tk::WireSegAddr a =
+        tk::wire_seg_addr(s, kind, (const char*)image + recs[s.rec].offset,
+                          recs[s.rec].diff ? (const char*)image + recs[s.rec - 1].offset : nullptr);
     const uint32_t start = (uint32_t)(cursor / 64);
     std::memcpy((char*)wire + 4 * i, &start, 4);
-    const int64_t len = kind == tk::kWireI32 ? tk::encode_seg(src, prev, s.n, payload + cursor)
-                                             : tk::encode_seg8(src, prev, s.n, kind, payload + cursor);
+    const int64_t len = kind == tk::kWireI32 ? tk::encode_seg(a.at, a.prev, s.n, payload + cursor)
+                                             : tk::encode_seg8(a.at, a.prev, s.n, kind, payload + cursor);
     const int64_t padded = tk::wire_align(len, 64);
     std::memset(payload + cursor + len, 0, (size_t)(padded - len));
     cursor += padded;
@@ -392,9 +385,8 @@ int64_t tk_wire_encode_host(const tk_wire_record* recs, int n_recs, const void* 
 
 int tk_wire_decode(const tk_wire_record* recs, int n_recs, const void* wire, int64_t wire_bytes, void* image,
                    int64_t image_bytes, int threads) {
-  tk::HostPlan p;
-  const int rc = tk::host_plan(recs, n_recs, image_bytes, &p, "tk_wire_decode");
-  if (rc) return rc;
+  tk::WirePlan p;
+  if (const int rc = tk::wire_plan(recs, n_recs, image_bytes, "tk_wire_decode", &p)) return rc;
   if (!wire || !image || wire_bytes < 0) {
     tk::set_error("tk_wire_decode: null buffer");
     return TK_ERR_INVALID_ARG;
@@ -402,19 +394,13 @@ int tk_wire_decode(const tk_wire_record* recs, int n_recs, const void* wire, int
   std::vector<tk::WireSegHost> segs(p.segs.size());
   for (size_t i = 0; i < p.segs.size(); ++i) {
     const tk::WireSegRef& s = p.segs[i];
-    const int64_t e0 = tk::wire_elem_bytes(recs[s.rec].kind) * s.e0;
-    segs[i].dst = (char*)image + recs[s.rec].offset + e0;
-    segs[i].prev = recs[s.rec].diff ? (const char*)image + recs[s.rec - 1].offset + e0 : nullptr;
-    segs[i].n = s.n;
-    segs[i].kind = recs[s.rec].kind;
+    const tk::WireSegAddr a =
+        tk::wire_seg_addr(s, recs[s.rec].kind, (char*)image + recs[s.rec].offset,
+                          recs[s.rec].diff ? (const char*)image + recs[s.rec - 1].offset : nullptr);
+    segs[i] = {a.at, a.prev, s.n, recs[s.rec].kind};
   }
-  tk::WireJob job;
-  job.wire = (const char*)wire;
-  job.wire_bytes = wire_bytes;
-  job.segs = segs.data();
-  job.n_seg = (int64_t)segs.size();
-  job.units = p.units.data();
-  job.n_units = (int64_t)p.units.size();
+  tk::WireJob job{(const char*)wire, wire_bytes, segs.data(), (int64_t)segs.size(),
+                  p.units.data(), (int64_t)p.units.size()};
   if (tk::wire_decode(&job, threads)) {
     tk::set_error("tk_wire_decode: the segment table or a segment does not lie inside the wire buffer");
     return TK_ERR_INVALID_ARG;
@@ -423,9 +409,8 @@ int tk_wire_decode(const tk_wire_record* recs, int n_recs, const void* wire, int
 }
 
 int tk_wire_check(const tk_wire_record* recs, int n_recs, const void* wire, int64_t wire_bytes) {
-  tk::HostPlan p;
-  const int rc = tk::host_plan(recs, n_recs, -1, &p, "tk_wire_check");
-  if (rc) return rc;
+  tk::WirePlan p;
+  if (const int rc = tk::wire_plan(recs, n_recs, -1, "tk_wire_check", &p)) return rc;
   const int64_t n_seg = (int64_t)p.segs.size();
   const int64_t table = tk::wire_table_bytes(n_seg);
   if (!wire || wire_bytes < table) {

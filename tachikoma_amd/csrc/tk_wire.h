@@ -1,8 +1,8 @@
 // Trace wire format: int32 trace records leave the device losslessly narrowed and are widened
 // on the host; 1-byte records that are a clamp of the record before them leave as that statement
-// and are rebuilt on the host (tk_wire.cc: host decoder, thread pool and reference encoder;
-// tk_elementwise.hip: the device encoder and the device decoder that verifies and loads trace files;
-// tk_runtime.cc: the packed capture that uses them).
+// and are rebuilt on the host (tk_wire.cc: the planner, host decoder, thread pool and reference
+// encoder; tk_trace.hip: the device encoder, the device decoder that verifies and loads trace files
+// and their entry points; tk_runtime.cc: the packed capture that uses them).
 //
 // A record of n int32 elements is cut into blocks of kWireBlock elements and segments of
 // kWireSegBlocks blocks (the last block / segment of a record may be short).  The coded value of
@@ -34,6 +34,8 @@
 #include <stdint.h>
 
 #include <vector>
+
+#include "../../include/tachikoma.h"
 
 namespace tk {
 
@@ -100,11 +102,26 @@ struct WireSegRef {
   int64_t e0;  // first element
 };
 
-// Segments and decode units of a run of records (diff[i]: record i is decoded after the same
-// segment of record i - 1, which then has the same element count: differenced against it, or
-// clamp-predicted from it).  Segments count elements, whatever their size.
-void wire_layout(const int64_t* n_elems, const int32_t* diff, int n_recs, std::vector<WireSegRef>* segs,
-                 std::vector<WireUnit>* units);
+// The plan of a run of records: segments, decode units (record i with `diff` is decoded after the
+// same segment of record i - 1, which has its kind and element count: differenced against it, or
+// clamp-predicted from it) and the wire buffer's size with every block raw.  Segments count elements.
+struct WirePlan {
+  std::vector<WireSegRef> segs;
+  std::vector<WireUnit> units;
+  int64_t bound = 0;
+};
+// Plans `recs` for the entry point `who`, offsets held to an image of image_bytes (-1: not looked
+// at).  An unknown kind, a record of no size or outside the image, a `diff` across a change of size
+// or kind, 2^31 segments or more: sets the error under `who`'s name and returns the status.
+int wire_plan(const tk_wire_record* recs, int n_recs, int64_t image_bytes, const char* who, WirePlan* plan);
+
+// Where a segment starts in its record's buffer and in its predecessor's (a null base gives null).
+// Whether the two are chained in the decode order is the plan's `diff`: another plan may hold the predecessor.
+struct WireSegAddr { char* at; const char* prev; };
+inline WireSegAddr wire_seg_addr(const WireSegRef& s, int kind, const void* base, const void* prev_base) {
+  const int64_t b0 = wire_elem_bytes(kind) * s.e0;
+  return {base ? (char*)base + b0 : nullptr, prev_base ? (const char*)prev_base + b0 : nullptr};
+}
 
 // Unrounded length of a segment of n elements of `kind` placed at table entry `start`, from the
 // widths its header states; -1 if start, header or length leave the payload or a width is not one

@@ -209,7 +209,7 @@ def read_trace(path_or_bytes, copy: bool = False) -> Trace:
 
 
 # ---------------------------------------------------------------- digests
-# Host twin of the device digest (tk_digest_bytes, csrc/tk_elementwise.hip):
+# Host twin of the device digest (tk_digest_bytes, csrc/tk_trace.hip):
 #   D(bytes) = Σ_i splitmix64_final(w_i ^ i·0x9E3779B97F4A7C15)  mod 2^64
 # over little-endian 8-byte words w_i, the tail zero-padded.  The trace digest of a
 # shard is D over the u64 array [D(record_0), D(record_1), ...] in record order, so

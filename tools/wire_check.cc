@@ -2,8 +2,9 @@
 // tests/test_wire_codec.py and tests/test_wire_codec8.py restated in C++ with heap buffers of exactly the sizes the codec may
 // touch, so that AddressSanitizer sees any byte read past a wire buffer or written outside a
 // record, and UBSan any overflowing or misaligned access; tk_wire_check, the host gate of the device
-// decoder, is held to the decoder's verdict on every valid and damaged buffer.  CPU only; never
-// needs a device.
+// decoder, is held to the decoder's verdict on every valid and damaged buffer; tk::wire_plan and
+// tk::wire_seg_addr, which every encoder and decoder lays its records out with, are called
+// directly.  CPU only; never needs a device.
 //
 //   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -pthread \
 //       -I include tools/wire_check.cc tachikoma_amd/csrc/tk_wire.cc -o wire_check && ./wire_check
@@ -18,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "../tachikoma_amd/csrc/tk_wire.h"
 #include "tachikoma.h"
 
 namespace tk {
@@ -221,7 +223,89 @@ static void byte_cases(int n) {
   }
 }
 
+// tk::wire_plan refuses `r` with `status`, under the caller's name
+static bool refused(const std::vector<tk_wire_record>& r, int64_t image_bytes, int status = TK_ERR_INVALID_ARG) {
+  tk::WirePlan p;
+  tk::g_err.clear();
+  return tk::wire_plan(r.data(), (int)r.size(), image_bytes, "some_caller", &p) == status &&
+         tk::g_err.rfind("some_caller: ", 0) == 0;
+}
+
+// The planner every encoder and decoder lays its records out with, and the address helper.
+static void planner_cases() {
+  const int seg = tk::kWireSegElems;
+  {  // a chain of three int32 records, one element longer than a segment
+    const int64_t n = seg + 1;
+    const std::vector<tk_wire_record> r = {{0, n, 0, 0}, {4 * n, n, 1, 0}, {8 * n, n, 1, 0}};
+    tk::WirePlan p;
+    CHECK(tk::wire_plan(r.data(), 3, 12 * n, "t", &p) == TK_OK);
+    CHECK(p.segs.size() == 6 && p.units.size() == 2);
+    for (size_t i = 0; i < p.segs.size(); ++i)
+      CHECK(p.segs[i].rec == (int)i / 2 && p.segs[i].n == (i % 2 ? 1 : seg) && p.segs[i].e0 == (int64_t)(i % 2) * seg);
+    for (size_t u = 0; u < p.units.size(); ++u)
+      CHECK(p.units[u].first == (int)u && p.units[u].stride == 2 && p.units[u].count == 3);
+    CHECK(p.bound == tk_wire_bound(r.data(), 3));
+    CHECK(p.bound == 64 + 3 * (tk::wire_seg_bound(seg) + tk::wire_seg_bound(1)));
+    CHECK(refused(r, 12 * n - 1));  // the last record's extent leaves the image
+    // the helper: byte offsets of 4-byte elements; a null base gives null
+    std::vector<char> rec(4 * n), prev(4 * n);
+    if (p.segs.size() == 6) {
+      const tk::WireSegAddr a = tk::wire_seg_addr(p.segs[3], 0, rec.data(), prev.data());
+      CHECK(a.at == rec.data() + 4 * (int64_t)seg && a.prev == prev.data() + 4 * (int64_t)seg);
+      const tk::WireSegAddr b = tk::wire_seg_addr(p.segs[3], 0, nullptr, nullptr);
+      CHECK(b.at == nullptr && b.prev == nullptr);
+    }
+  }
+  {  // chains cut by a record of another kind: int32, int8 and uint8 in one plan
+    const int64_t n = seg + 5, m = 300;
+    const std::vector<tk_wire_record> r = {{0, n, 0, 0}, {0, n, 1, 0}, {0, m, 0, 1}, {0, m, 1, 1}, {0, m, 0, 2}, {0, n, 0, 0}};
+    tk::WirePlan p;
+    CHECK(tk::wire_plan(r.data(), 6, -1, "t", &p) == TK_OK);
+    const int want_rec[9] = {0, 0, 1, 1, 2, 3, 4, 5, 5};
+    const int want_n[9] = {seg, 5, seg, 5, 300, 300, 300, seg, 5};
+    CHECK(p.segs.size() == 9);
+    for (size_t i = 0; i < p.segs.size() && i < 9; ++i)
+      CHECK(p.segs[i].rec == want_rec[i] && p.segs[i].n == want_n[i] && p.segs[i].e0 == (want_n[i] == 5 ? seg : 0));
+    const tk::WireUnit want_units[6] = {{0, 2, 2}, {1, 2, 2}, {4, 1, 2}, {6, 1, 1}, {7, 2, 1}, {8, 2, 1}};
+    CHECK(p.units.size() == 6);
+    for (size_t u = 0; u < p.units.size() && u < 6; ++u)
+      CHECK(p.units[u].first == want_units[u].first && p.units[u].stride == want_units[u].stride &&
+            p.units[u].count == want_units[u].count);
+    CHECK(p.bound == tk_wire_bound(r.data(), 6));
+    CHECK(p.bound == 64 + 3 * (tk::wire_seg_bound(seg) + tk::wire_seg_bound(5)) + 3 * tk::wire_seg_bound(300, 1));
+  }
+  {  // an unchained 1-byte record whose predecessor another plan holds: the helper still gives the
+     // predecessor's address, the units do not chain it
+    const int64_t n = seg + 10;
+    const tk_wire_record r{0, n, 0, 2};
+    tk::WirePlan p;
+    CHECK(tk::wire_plan(&r, 1, -1, "t", &p) == TK_OK);
+    CHECK(p.segs.size() == 2 && p.units.size() == 2);
+    for (size_t u = 0; u < p.units.size(); ++u) CHECK(p.units[u].first == (int)u && p.units[u].count == 1);
+    std::vector<char> rec(n), prev(n);
+    if (p.segs.size() == 2) {
+      const tk::WireSegAddr a = tk::wire_seg_addr(p.segs[1], r.kind, rec.data(), prev.data());
+      CHECK(a.at == rec.data() + seg && a.prev == prev.data() + seg);
+      CHECK(tk::wire_seg_addr(p.segs[1], r.kind, rec.data(), nullptr).prev == nullptr);
+    }
+  }
+  // the refusals, each under the caller's name
+  CHECK(refused({{0, 8, 1, 0}}, -1));                                  // record 0 with diff
+  CHECK(refused({{0, 8, 0, 0}, {32, 9, 1, 0}}, -1));                   // diff across a change of size
+  CHECK(refused({{0, 8, 0, 1}, {8, 8, 1, 2}}, -1));                    // ... of kind
+  CHECK(refused({{0, 0, 0, 0}}, -1));                                  // no elements
+  CHECK(refused({{0, ((int64_t)1 << 40) + 1, 0, 1}}, -1));             // too many
+  CHECK(refused({{0, 8, 0, 3}}, -1) && refused({{0, 8, 0, -1}}, -1));  // unknown kinds
+  CHECK(refused({{-1, 8, 0, 0}}, -1) && refused({{-1, 8, 0, 0}}, 64));
+  CHECK(refused({{65, 8, 0, 1}}, 64));                                 // an offset outside the image
+  CHECK(refused({{36, 8, 0, 0}}, 64) && !refused({{32, 8, 0, 0}}, 64));  // an extent outside it
+  CHECK(refused({}, -1));
+  // 2^31 segments: refused before anything is laid out
+  CHECK(refused(std::vector<tk_wire_record>(32, tk_wire_record{0, (int64_t)1 << 40, 0, 1}), -1, TK_ERR_UNSUPPORTED));
+}
+
 int main() {
+  planner_cases();
   for (int n : {1, 15, 16, 17, 255, 256, 257, 3 * 256 + 17, 2 * 16384 + 300}) byte_cases(n);
   const int sizes[] = {1, 255, 256, 257, 3 * 256 + 17, 2 * 16384 + 300};
   for (int n : sizes) {
