@@ -217,6 +217,19 @@ int tk_conv2d_pack_weight(const tk_tensor* weight, int groups, void* packed, int
  * pixels are contiguous), padded channels 0, uint8 data stored xor 0x80. */
 int64_t tk_conv2d_shadow_bytes(const tk_tensor* data);
 int tk_conv2d_make_shadow(const tk_tensor* data, void* shadow, void* stream);
+/* The shadows of n tensors in one launch: shadow[i] (16-byte aligned, tk_conv2d_shadow_bytes(data[i])
+ * bytes) becomes byte for byte what tk_conv2d_make_shadow(data[i], shadow[i]) writes.  It replaces a
+ * loop of n such calls where a module's record buffers were filled from a trace file and every
+ * shadow derived from a record has to be rebuilt (GraphModule.replay_trace, load_trace(shadows=True));
+ * the shadow node of the traced step keeps tk_conv2d_make_shadow.  One wave per (tensor, image,
+ * 16-channel chunk, 256-pixel tile): 16 lanes load 16 channels of 16 consecutive pixels with the
+ * widest loads each plane's address allows, transpose through LDS and store 16 bytes per pixel.  The
+ * item table is laid out and uploaded when a list of tensors (addresses, shapes, dtypes) is first
+ * seen and kept on the device for later calls with the same list.  Asynchronous on `stream`, never
+ * synchronises (except that the table of a list not used for a long time is freed when room is made
+ * for a new one).  n == 0: TK_OK, nothing launched.  A null pointer, a tensor that is not compact
+ * 4-D int8/uint8 or a shadow that is not 16-byte aligned: TK_ERR_INVALID_ARG. */
+int tk_conv2d_make_shadow_batch(const tk_tensor* const* data, void* const* shadow, int n, void* stream);
 /* Device scratch of a prepared conv (tk_qnn_conv2d_prepared: block = 0; tk_qnn_conv2d_block:
  * block = 1): per-pixel patch sums when the kernel zero point is non-zero, plus split-K
  * partial tiles for layers whose tile grid cannot fill the GPU, or (3x3 blocks) up to four
@@ -784,6 +797,12 @@ int tk_compare_device_batch(const void* const* expected, const void* const* got,
 int tk_module_wait_capture(tk_module* mod, void* stream);
 /* Runs nodes [begin, end) only (per-op record-and-run, Trace.calibrate analogue). */
 int tk_module_run_range(tk_module* mod, int begin, int end, void* stream);
+/* Runs the n nodes order[0..n) in that order (a node may appear more than once): the replay of a
+ * loaded trace runs the nodes in reverse so that each reads recorded inputs.  Waits for the last
+ * traced run's copies like tk_module_run_range; no capture.  A null module, n < 0, a null order
+ * with n > 0 or an index outside [0, tk_module_num_nodes) is TK_ERR_INVALID_ARG before any node
+ * runs. */
+int tk_module_run_order(tk_module* mod, const int32_t* order, int n, void* stream);
 /* Runs once with a timing event after every node and returns per-node device time in
  * milliseconds (GraphExecutorDebug::RunIndividual analogue, graph_executor_debug.cc:70-116). */
 int tk_module_run_profiled(tk_module* mod, void* stream, float* node_ms);

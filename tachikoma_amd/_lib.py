@@ -370,6 +370,7 @@ SIGNATURES = {
     "tk_conv2d_shadow_bytes": (_I64, [_PT]),
     "tk_conv2d_scratch_bytes": (_I64, [_PT, _PT, ctypes.POINTER(tk_conv2d_attrs), ctypes.c_int]),
     "tk_conv2d_make_shadow": (ctypes.c_int, [_PT, _VP, _VP]),
+    "tk_conv2d_make_shadow_batch": (ctypes.c_int, [ctypes.POINTER(_PT), ctypes.POINTER(_VP), ctypes.c_int, _VP]),
     "tk_qnn_conv2d_prepared": (ctypes.c_int, [_PT, _VP, _PT, _VP, _VP, _PT, ctypes.POINTER(tk_conv2d_attrs), _VP,
                                               _VP]),
     "tk_qnn_conv2d_workspace_bytes": (_I64, [_PT, _PT, ctypes.POINTER(tk_conv2d_attrs)]),
@@ -420,6 +421,7 @@ SIGNATURES = {
     "tk_module_run": (ctypes.c_int, [_VP, _VP, _VP, ctypes.POINTER(_VP)]),
     "tk_module_wait_capture": (ctypes.c_int, [_VP, _VP]),
     "tk_module_run_range": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, _VP]),
+    "tk_module_run_order": (ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_int32), ctypes.c_int, _VP]),
     "tk_module_run_profiled": (ctypes.c_int, [_VP, _VP, ctypes.POINTER(_F32)]),
     "tk_module_set_profiling": (ctypes.c_int, [_VP, ctypes.c_int]),
     "tk_module_node_times": (ctypes.c_int, [_VP, ctypes.POINTER(_F32)]),

@@ -238,6 +238,7 @@ class Mismatch:
     count: int                    # differing elements
     flat_index: int               # the first of them
     first_index: Tuple[int, ...]  # the same, unravelled
+    node: int = -1                # replay_trace: index of the node that writes the record
 
 
 class VerifyReport:
@@ -267,6 +268,40 @@ class VerifyReport:
     def __repr__(self):
         return (f"VerifyReport(ok={self.ok}, n_records={self.n_records}, mismatched={len(self.mismatches)}, "
                 f"first={self.first.name if self.first else None}, params_equal={self.params_equal})")
+
+
+@dataclass
+class FaultyNode:
+    """One node of a replay with at least one record that differs from the file."""
+    node: int                  # index in the native module's node list
+    kind: str                  # DeviceModule.node_kinds: "conv_block", "add_block", an op name, ...
+    records: Tuple[str, ...]   # the node's records in chain order
+    first: str                 # the first of them that differs
+
+
+class ReplayReport(VerifyReport):
+    """What GraphModule.replay_trace returns.  A mismatch here means "this record is not what this
+    engine computes from the file's recorded inputs of its node": every node ran on what the file
+    recorded, not on what the node before it computed, so a fault stays in the node it occurs in
+    and an independent fault behind it is reported too.  Graph-input records are loaded, not
+    computed, and are never listed.  ``nodes``: one FaultyNode per node with a differing record, in
+    node order; ``first`` is the first faulty node's first differing record.  The granularity is the
+    node: within a fused node (conv -> bias_add -> requantize -> [add] -> [clip]) the ops read one
+    another's values inside one kernel, so a fault still runs down the chain from the op it occurs
+    in.  ``detail(m)`` gives the file's value and the recomputed one (the buffers hold the replayed
+    values).  ``stats`` adds store_ms, shadow_ms, replay_ms (HIP events) and shadows (the number of
+    shadows rebuilt up front) to VerifyReport's."""
+
+    def __init__(self, verifier, source, n_records, mismatches, params_differing, stats, nodes):
+        super().__init__(verifier, source, n_records, mismatches, params_differing, stats)
+        self.nodes: List[FaultyNode] = nodes
+        if nodes:
+            self.first = next(m for m in mismatches if m.name == nodes[0].first)
+
+    def __repr__(self):
+        return (f"ReplayReport(ok={self.ok}, n_records={self.n_records}, mismatched={len(self.mismatches)}, "
+                f"faulty_nodes={[n.node for n in self.nodes]}, first={self.first.name if self.first else None}, "
+                f"params_equal={self.params_equal})")
 
 
 class TraceVerifier:
@@ -792,18 +827,64 @@ class GraphModule:
         stats["compare_ms"] = (time.perf_counter() - t1) * 1e3
         return VerifyReport(v, path_or_bytes, len(ct.entries), v.mismatches(ct, found), params_differing, stats)
 
-    def load_trace(self, path_or_bytes) -> None:
+    def replay_trace(self, path_or_bytes) -> ReplayReport:
+        """Re-execute every op of a trace file from its recorded inputs and compare, on the device.
+        Reading, the host checks and the upload are verify_trace's (a damaged file is a ValueError
+        before anything reaches the device).  Then every record of the file is stored into the
+        module's buffers (as load_trace does), the shadows whose source is a record are rebuilt in
+        one launch (tk_conv2d_make_shadow_batch), the nodes run in the order of relay/replay.py
+        (record-producing nodes in reverse, each after the helper nodes it needs:
+        tk_module_run_order), and one compare pass over the whole file gives the verdict of every
+        node at once (ReplayReport).  The nodes compute with the module's own params and packed
+        weights; the file's params are compared and reported as by verify_trace.  Afterwards the
+        buffers hold the replayed values, not a run's: the next run() overwrites everything."""
+        import torch
+        v = self.trace_verifier()
+        order, shadows = self.module.replay_plan()  # (UnsupportedError before anything is touched)
+        ct, stats = v.stage(path_or_bytes)
+        stream = torch.cuda.current_stream(self.module.device)
+        v.upload(ct, stream, stats)
+        t0 = time.perf_counter()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        ev[0].record(stream)
+        v.store(ct, {e.name for e in ct.entries}, stream)
+        ev[1].record(stream)
+        self.module.rebuild_shadows(shadows, stream)
+        ev[2].record(stream)
+        self.module.run_order(order, stream)
+        ev[3].record(stream)
+        stream.synchronize()
+        t1 = time.perf_counter()
+        found, params_differing = v.compare(ct, stream)
+        stats["store_ms"], stats["shadow_ms"], stats["replay_ms"] = (ev[k].elapsed_time(ev[k + 1]) for k in range(3))
+        stats["shadows"] = len(shadows)
+        stats["run_ms"] = (t1 - t0) * 1e3
+        stats["compare_ms"] = (time.perf_counter() - t1) * 1e3
+        node_of = {r: i for i, recs in enumerate(self.module.node_records) for r in recs}
+        mismatches = [m for m in v.mismatches(ct, found) if m.name not in v.inputs]
+        for m in mismatches:
+            m.node = node_of.get(m.name, -1)
+        bad = {m.name for m in mismatches}
+        nodes = [FaultyNode(i, self.module.node_kinds[i], tuple(recs), next(r for r in recs if r in bad))
+                 for i, recs in enumerate(self.module.node_records) if any(r in bad for r in recs)]
+        return ReplayReport(v, path_or_bytes, len(ct.entries), mismatches, params_differing, stats, nodes)
+
+    def load_trace(self, path_or_bytes, shadows: bool = False) -> None:
         """Put a trace file's records into the module's record buffers (the reading and the checks
         of verify_trace, then the decoder's store mode and device-to-device copies), so that
-        get_node_output(name) returns what the file recorded.  Params are left alone.  The
-        shadows and other buffers derived from records are NOT rebuilt, and the next run()
-        overwrites every record."""
+        get_node_output(name) returns what the file recorded.  Params are left alone.  With
+        ``shadows`` the shadows whose source is a record are rebuilt from the loaded records
+        (tk_conv2d_make_shadow_batch), so that module.run_range from any node works on loaded
+        data; without it the shadows and other buffers derived from records are NOT rebuilt.  The
+        next run() overwrites every record."""
         import torch
         v = self.trace_verifier()
         ct, stats = v.stage(path_or_bytes)
         stream = torch.cuda.current_stream(self.module.device)
         v.upload(ct, stream, stats)
         v.store(ct, {e.name for e in ct.entries}, stream)
+        if shadows:
+            self.module.rebuild_shadows(None, stream)
         stream.synchronize()
 
     def trace_digest(self) -> int:

@@ -1326,6 +1326,26 @@ int tk_module_run_range(tk_module* mod, int begin, int end, void* stream) {
   return TK_OK;
 }
 
+int tk_module_run_order(tk_module* mod, const int32_t* order, int n, void* stream) {
+  if (!mod || n < 0 || (n > 0 && !order)) {
+    tk::set_error("tk_module_run_order: null module, negative count or null order");
+    return TK_ERR_INVALID_ARG;
+  }
+  for (int k = 0; k < n; ++k)
+    if (order[k] < 0 || order[k] >= (int)mod->nodes.size()) {
+      tk::set_error("tk_module_run_order: node index " + std::to_string(order[k]) + " out of range");
+      return TK_ERR_INVALID_ARG;
+    }
+  hipStream_t s = tk::as_stream(stream);
+  int rc0 = wait_capture(mod, s);
+  if (rc0) return rc0;
+  for (int k = 0; k < n; ++k) {
+    int rc = tk::run_node(mod->nodes[order[k]], s);
+    if (rc) return rc;
+  }
+  return TK_OK;
+}
+
 int tk_module_run_profiled(tk_module* mod, void* stream, float* node_ms) {
   if (!mod || !node_ms) {
     tk::set_error("tk_module_run_profiled: invalid argument");

@@ -29,8 +29,7 @@ from .qnn import op as _qnn
 TARGETS = ("mi355x", "rocm", "hip", "gfx950")
 
 
-class UnsupportedError(NotImplementedError):
-    pass
+from .replay import UnsupportedError  # noqa: E402,F401  (one class for the whole package)
 
 
 @dataclass

@@ -85,6 +85,11 @@ class DeviceModule:
         self.node_records: List[List[str]] = []  # tk node index -> record names of its outputs
         self.node_kinds: List[str] = []
         self.node_native_kinds: List[int] = []  # tk_node kind (TK_NODE_*) of each node
+        # per node: the buffers it reads and writes, by name (relay/replay.py: the plain data the
+        # replay schedule is computed from); shadows are "shadow:<tensor>", scratch "<op>:<what>"
+        self.node_io: List[dict] = []
+        # shadow name -> (TensorRef of its source as the kernels see it, the shadow's buffer)
+        self.shadow_sources: Dict[str, tuple] = {}
         # param name -> re-derivations of the build-time buffers computed from it (packed MFMA
         # weights + weight sums), re-run whenever the param's device copy is rewritten
         self._derived: Dict[str, List[Callable[[int], None]]] = {}
@@ -335,13 +340,36 @@ class DeviceModule:
         pool_names = {op.name for op in pool_ops}
         shadow_ready = set()
 
-        def emit(n, kind, records):
+        for name, buf in shadow_bufs.items():
+            self.shadow_sources[f"shadow:{name}"] = (self._ref(name), buf)
+        consts = {t.name for t in self.plan.params}
+        # what the node being built reads / writes beside its plan inputs and records: the shadow
+        # it reads (ensure_shadow) and the one its epilogue writes (shadow_out); taken by its emit
+        pending = {"reads": [], "writes": []}
+
+        def emit(n, kind, records, reads=(), writes=(), shadows=None):
             nodes.append(n)
             self.node_kinds.append(kind)
             self.node_native_kinds.append(int(n.kind))
             self.node_records.append(records)
+            io = {"kind": kind, "records": list(records),
+                  "reads": [x for x in dict.fromkeys(reads) if x not in consts],
+                  "writes": list(dict.fromkeys(list(records) + list(writes))), "shadows": dict(shadows or {})}
+            if kind != "shadow":
+                io["reads"] += [x for x in pending["reads"] if x not in io["reads"]]
+                for s in pending["writes"]:
+                    io["writes"].append(s)
+                    io["shadows"][s] = s[len("shadow:"):]
+                pending["reads"], pending["writes"] = [], []
+            self.node_io.append(io)
+
+        def shadow_out(name: str):
+            """The node being built writes the shadow of its output ``name``."""
+            shadow_ready.add(name)
+            pending["writes"].append(f"shadow:{name}")
 
         def ensure_shadow(name: str):
+            pending["reads"].append(f"shadow:{name}")
             if name in shadow_ready:
                 return
             sn = _lib.tk_node()
@@ -350,7 +378,7 @@ class DeviceModule:
             sn.inputs[0] = self._ref(name).ptr
             sn.n_outputs = 0
             sn.ext[0] = shadow_bufs[name].data_ptr()
-            emit(sn, "shadow", [])
+            emit(sn, "shadow", [], [name], [f"shadow:{name}"], {f"shadow:{name}": name})
             shadow_ready.add(name)
 
         for g in self.groups:
@@ -383,9 +411,9 @@ class DeviceModule:
                     if g.last.name in shadow_bufs:
                         # the epilogue writes the shadow the next MFMA conv reads
                         n.ext[4] = shadow_bufs[g.last.name].data_ptr()
-                        shadow_ready.add(g.last.name)
+                        shadow_out(g.last.name)
                 elif self._dense_as_conv(n, g, head, ins, outs, emit, stream):
-                    pass
+                    pending["reads"].append(f"shadow:{head.name}:in")  # the shadow node it emitted
                 else:
                     n.kind = _lib.NODE_KINDS["dense_block"]
                     self._dense_attrs(ba.dense, head)
@@ -401,7 +429,7 @@ class DeviceModule:
                     ab.clip_min, ab.clip_max = g.ops[1].attrs["lo"], g.ops[1].attrs["hi"]
                 if g.last.name in shadow_bufs and len(head.out.shape) == 4:
                     n.ext[4] = shadow_bufs[g.last.name].data_ptr()
-                    shadow_ready.add(g.last.name)
+                    shadow_out(g.last.name)
             else:
                 op = head
                 kind = op.op
@@ -513,7 +541,7 @@ class DeviceModule:
                         n.ext[0] = shadow_bufs[op.inputs[0]].data_ptr()
                         if op.name in shadow_bufs:
                             n.ext[4] = shadow_bufs[op.name].data_ptr()
-                            shadow_ready.add(op.name)
+                            shadow_out(op.name)
                     pa = n.attrs.pool2d
                     pa.pool_size[:] = list(a["pool_size"])
                     pa.strides[:] = list(a["strides"])
@@ -561,7 +589,8 @@ class DeviceModule:
             n.n_outputs = len(outs)
             for k, r in enumerate(outs):
                 n.outputs[k] = r.ptr
-            emit(n, g.kind, [o.name for o in g.ops])
+            own = {o.name for o in g.ops}
+            emit(n, g.kind, [o.name for o in g.ops], [x for o in g.ops for x in o.inputs if x not in own])
         torch.cuda.current_stream().synchronize()
         self._node_kind_codes = [int(n.kind) for n in nodes]
         self._nodes = nodes  # (their tensors and attrs describe a node's kernels: algo_info)
@@ -608,7 +637,7 @@ class DeviceModule:
             t.attrs.transpose = self._transpose_attrs(perm)
             t.n_inputs, t.n_outputs = 1, 1
             t.inputs[0], t.outputs[0] = self._ref(src).ptr, self._ref(dst).ptr
-            emit(t, "transpose", records)
+            emit(t, "transpose", records, [src], [dst])
 
         if L["x"] != op.inputs[0]:
             transpose_node(op.inputs[0], L["x"], self._TO_NCHW, [])
@@ -619,7 +648,7 @@ class DeviceModule:
         n.n_inputs, n.n_outputs = 2, 1
         n.inputs[0], n.inputs[1] = ins[0].ptr, ins[1].ptr
         n.outputs[0] = self._ref(L["y"]).ptr
-        emit(n, "qnn.conv2d", [] if L["y"] != op.name else [op.name])
+        emit(n, "qnn.conv2d", [] if L["y"] != op.name else [op.name], [L["x"]], [L["y"]])
         if L["y"] != op.name:
             transpose_node(L["y"], op.name, self._TO_NHWC, [op.name])
 
@@ -635,7 +664,7 @@ class DeviceModule:
             t.attrs.transpose = self._transpose_attrs(perm)
             t.n_inputs, t.n_outputs = 1, 1
             t.inputs[0], t.outputs[0] = self._ref(src).ptr, self._ref(dst).ptr
-            emit(t, "transpose", records)
+            emit(t, "transpose", records, [src], [dst])
 
         if L["x"] != op.inputs[0]:
             transpose_node(op.inputs[0], L["x"], self._TO_NCHW, [])
@@ -652,7 +681,7 @@ class DeviceModule:
         n.n_inputs, n.n_outputs = 2, 1
         n.inputs[0], n.inputs[1] = self._ref(L["x"]).ptr, self._ref(L["w"]).ptr
         n.outputs[0] = self._ref(L["y"]).ptr
-        emit(n, "qnn.conv2d_transpose", [] if L["y"] != op.name else [op.name])
+        emit(n, "qnn.conv2d_transpose", [] if L["y"] != op.name else [op.name], [L["x"]], [L["y"]])
         if L["y"] != op.name:
             transpose_node(L["y"], op.name, self._TO_NHWC, [op.name])
 
@@ -691,7 +720,9 @@ class DeviceModule:
         sn.inputs[0] = x4.ptr
         sn.n_outputs = 0
         sn.ext[0] = shadow.data_ptr()
-        emit(sn, "shadow", [])
+        sname = f"shadow:{head.name}:in"
+        self.shadow_sources[sname] = (x4, shadow)
+        emit(sn, "shadow", [], [head.inputs[0]], [sname], {sname: head.inputs[0]})
         packed = self._scratch(self.lib.tk_conv2d_packed_weight_bytes(w4.ptr, 1))
         sums = self._scratch(((u + 127) // 128 * 128) * 4)
         self._pack(head.inputs[1], head.name, w4, packed, sums, stream)
@@ -731,7 +762,8 @@ class DeviceModule:
         c.inputs[0], c.inputs[1] = ins[0].ptr, ins[1].ptr
         c.n_outputs = 1
         c.outputs[0] = acc_ref.ptr
-        emit(c, op.op + ":contraction", [])  # not a record
+        acc_name = f"{op.name}:acc"
+        emit(c, op.op + ":contraction", [], [op.inputs[0]], [acc_name])  # not a record
         p = _lib.tk_node()
         p.kind = _lib.NODE_KINDS["postops"]
         pa = p.attrs.postops
@@ -750,7 +782,7 @@ class DeviceModule:
             p.inputs[1] = self._ref(op.inputs[2]).ptr
         p.n_outputs = 1
         p.outputs[0] = self._ref(op.name).ptr
-        emit(p, op.op, [op.name])
+        emit(p, op.op, [op.name], [acc_name] + ([op.inputs[2]] if a["has_sum"] else []))
 
     def _pack(self, param: str, what: str, weight: _lib.TensorRef, packed, sums, stream) -> None:
         """Pack an MFMA conv weight (and its per-channel sums) now, and register the packing
@@ -898,6 +930,37 @@ class DeviceModule:
         """Nodes [begin, end) only, on ``stream`` (tk_module_run_range; no capture)."""
         _lib.check(self.lib.tk_module_run_range(self.handle, int(begin), int(end),
                                                 ctypes.c_void_p(_lib.stream_handle(stream))), "tk_module_run_range")
+
+    def run_order(self, order, stream=None) -> None:
+        """The nodes ``order`` in that order, on ``stream`` (tk_module_run_order; no capture)."""
+        arr = (ctypes.c_int32 * max(1, len(order)))(*[int(i) for i in order])
+        _lib.check(self.lib.tk_module_run_order(self.handle, arr, len(order),
+                                                ctypes.c_void_p(_lib.stream_handle(stream))), "tk_module_run_order")
+
+    def replay_plan(self):
+        """(node order of a replay, names of the shadows to rebuild up front): relay/replay.py on
+        this module's ``node_io``, computed once."""
+        if getattr(self, "_replay_plan", None) is None:
+            from .replay import replay_order
+            self._replay_plan = replay_order(self.node_io, [t.name for t in self.plan.inputs])
+        return self._replay_plan
+
+    def rebuild_shadows(self, names=None, stream=None) -> int:
+        """Rebuild the shadows ``names`` (default: every shadow whose source is a record or a graph
+        input) from their sources as they stand, in one launch (tk_conv2d_make_shadow_batch).
+        Returns how many were rebuilt."""
+        names = self.replay_plan()[1] if names is None else list(names)
+        key = tuple(names)
+        cached = getattr(self, "_shadow_batch", None)
+        if cached is None or cached[0] != key:
+            n = len(names)
+            data = (ctypes.POINTER(_lib.tk_tensor) * max(1, n))(*[self.shadow_sources[s][0].ptr for s in names])
+            dst = (ctypes.c_void_p * max(1, n))(*[self.shadow_sources[s][1].data_ptr() for s in names])
+            self._shadow_batch = cached = (key, data, dst)
+        _lib.check(self.lib.tk_conv2d_make_shadow_batch(cached[1], cached[2], len(names),
+                                                        ctypes.c_void_p(_lib.stream_handle(stream))),
+                   "tk_conv2d_make_shadow_batch")
+        return len(names)
 
     def run_profiled(self, stream=None) -> Dict[str, float]:
         ms = (ctypes.c_float * self.n_nodes)()

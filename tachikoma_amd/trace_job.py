@@ -29,7 +29,9 @@ CLI (one process per GPU, torch.distributed.run environment; rank 0 writes the m
 
 ``--check`` traces nothing: it walks the rank's journal and verifies every chunk file against the
 engine on the device, record by record (:func:`check`, GraphModule.verify_trace), printing one JSON
-line per chunk; ``--verify`` keeps its meaning (re-digest the files a resumed job keeps).
+line per chunk; ``--verify`` keeps its meaning (re-digest the files a resumed job keeps).  ``--check
+--replay`` re-executes every op of each chunk from its recorded inputs instead
+(GraphModule.replay_trace) and adds the faulty nodes to the chunk's JSON line.
 """
 from __future__ import annotations
 
@@ -285,10 +287,11 @@ class GraphModuleTracer:
         self.busy[id(cap)] = fut
         return fut
 
-    def check(self, path: str):
-        """Verify one chunk file, packed or not, on the device (GraphModule.verify_trace): the
-        module is the one of the file's own ``n_samples``, and each module keeps one verifier.
-        Returns the VerifyReport; ValueError for a file that does not parse or is of another graph."""
+    def check(self, path: str, replay: bool = False):
+        """Verify one chunk file, packed or not, on the device (GraphModule.verify_trace; with
+        ``replay`` GraphModule.replay_trace: every op from its recorded inputs): the module is the
+        one of the file's own ``n_samples``, and each module keeps one verifier.  Returns the
+        VerifyReport / ReplayReport; ValueError for a file that does not parse or is of another graph."""
         with open(path, "rb") as f:
             head = f.read(56)
             jl = tf._header(head)[1]
@@ -298,7 +301,8 @@ class GraphModuleTracer:
                 raise ValueError(f"{path}: the trace header does not state n_samples") from None
         if not 1 <= n <= 1 << 20:
             raise ValueError(f"{path}: n_samples {n}")
-        return self._module(n, captures=False)[0].verify_trace(path)
+        m = self._module(n, captures=False)[0]
+        return m.replay_trace(path) if replay else m.verify_trace(path)
 
     def close(self) -> None:
         """Wait for the writer, then release every module (device first, then the native module:
@@ -313,16 +317,19 @@ class GraphModuleTracer:
 
 
 def check(tracer: GraphModuleTracer, out_dir: str, rank: int = 0, stem: str = "trace",
-          log: Optional[Callable[[str], None]] = None) -> List[dict]:
+          log: Optional[Callable[[str], None]] = None, replay: bool = False) -> List[dict]:
     """Verify every journalled chunk file of this rank against the engine, in chunk order, following
     each file's own version: one dict per chunk, {"chunk", "file", "ok", "n_mismatched", "first":
     {name, op, first_index} | None, "params_equal", **stats}.  A missing or unreadable file, or one
-    that does not parse or is of another graph, is ``ok: False`` with ``"error"``."""
+    that does not parse or is of another graph, is ``ok: False`` with ``"error"``.  With ``replay``
+    each chunk is replayed op by op from its recorded inputs instead (GraphModule.replay_trace) and
+    the dict also has "nodes": [{node, kind, records, first}] of the faulty nodes."""
     out = []
     for index, e in sorted(Journal(journal_file(out_dir, rank, stem)).entries().items()):
         row = {"chunk": index, "file": e.get("file")}
         try:
-            rep = tracer.check(os.path.join(out_dir, str(e.get("file"))))
+            path = os.path.join(out_dir, str(e.get("file")))
+            rep = tracer.check(path, replay=True) if replay else tracer.check(path)
         except (OSError, ValueError) as err:
             row.update(ok=False, error=f"{type(err).__name__}: {err}")
         else:
@@ -330,6 +337,9 @@ def check(tracer: GraphModuleTracer, out_dir: str, rank: int = 0, stem: str = "t
             row.update(ok=rep.ok, n_mismatched=len(rep.mismatches),
                        first=None if f is None else {"name": f.name, "op": f.op, "first_index": list(f.first_index)},
                        params_equal=rep.params_equal, **rep.stats)
+            if replay:
+                row["nodes"] = [{"node": n.node, "kind": n.kind, "records": list(n.records), "first": n.first}
+                                for n in rep.nodes]
         if log:
             log(f"rank {rank}: chunk {index} {'ok' if row['ok'] else 'FAILED'}")
         out.append(row)
@@ -349,7 +359,12 @@ def main(argv=None) -> int:
     p.add_argument("--check", action="store_true",
                    help="trace nothing: verify every journalled chunk file against the engine, record by record, "
                         "on the device; one JSON line per chunk, exit status 1 if any chunk fails")
+    p.add_argument("--replay", action="store_true",
+                   help="with --check: replay every chunk op by op from its recorded inputs instead, so that a "
+                        "fault stays in its node; the JSON line also lists the faulty nodes")
     args = p.parse_args(argv)
+    if args.replay and not args.check:
+        p.error("--replay goes with --check")
     import torch
     from . import relay, zoo
     from .contrib import graph_executor
@@ -372,7 +387,7 @@ def main(argv=None) -> int:
     log = lambda s: print(f"[trace_job] {s}", file=sys.stderr, flush=True)  # noqa: E731
     if args.check:
         try:
-            rows = check(tracer, args.out_dir, rank, log=log)
+            rows = check(tracer, args.out_dir, rank, log=log, replay=args.replay)
         finally:
             tracer.close()
             if world > 1:
