@@ -791,6 +791,52 @@ int tk_compare_device(const void* expected, const void* got, int64_t n_elems, in
 int tk_compare_device_batch(const void* const* expected, const void* const* got, const int64_t* n_elems,
                             const int32_t* elem_bytes, int n, tk_wire_mismatch* report, void* stream);
 
+/* The chain check: one verdict per op inside fused nodes.
+ *
+ * A conv, dense or add block writes its whole chain of records from one kernel
+ * (conv -> bias_add -> requantize -> [qnn.add] -> [clip]; add -> [clip]), so re-running the node
+ * can only say that the node differs.  Every op of the chain but the first (a *tail op*) is
+ * elementwise over records of the chain: bias_add of the conv record (int32 wrap-around add of
+ * bias[c] along axis 1), requantize of the bias_add record (the node's tk_requantize_attrs, then
+ * the saturating cast), qnn.add of the requantize record and the residual, clip of its predecessor.
+ * The check computes each tail op from its own recorded input AS IT STANDS in the buffers, with the
+ * device functions the fused epilogues use, and compares with the recorded output as it stands
+ * there: entry k of the report is the number of elements of tail op k's record that are not the op
+ * of its input, and the flat index of the first (~0 if none).  A wrong record therefore shows at
+ * its producer and possibly at its consumer, and nowhere further down.  Nothing is stored into a
+ * record.  The head op (conv / dense / the add of an add block) is not judged here.
+ *
+ * One launch takes every chain: a workgroup takes tk_chain_check_tile() consecutive elements of one
+ * chain, a lane four at a time (16 bytes of the int32 records, 4 of the 1-byte ones; element by
+ * element at a ragged end and where a buffer is not 16- / 4-byte aligned), each record read once.
+ *
+ * tk_module_chain_ops: the tail ops of the module's TK_NODE_CONV_BLOCK / TK_NODE_DENSE_BLOCK /
+ * TK_NODE_ADD_BLOCK nodes in report order -- node order, then chain order -- each as (node, index
+ * of the output it writes); fills at most `capacity` entries, returns how many exist.  A node with
+ * one record has no tail op.
+ * tk_module_check_chains: checks them on the module's buffers as they stand (after a trace file's
+ * records were stored there); report[k] belongs to op k of tk_module_chain_ops; returns the number
+ * of entries, TK_ERR_INVALID_ARG when `capacity` is smaller.  The table is laid out and uploaded
+ * by the first of the two calls and kept on the device with the module; later calls upload nothing.
+ * tk_check_chain: one chain described by plain tensors.  kind: TK_NODE_CONV_BLOCK /
+ * TK_NODE_DENSE_BLOCK (`records` = {conv, bias_add, requantize, [add], [clip]}, `bias` int32
+ * [channels], `attrs` a tk_block_attrs whose conv / dense / algo fields are not read and whose
+ * `residual` is the other qnn.add operand) or TK_NODE_ADD_BLOCK (`records` = {add, [clip]}, `bias`
+ * NULL, `attrs` a tk_add_block_attrs).  Records have one shape with the channels on axis 1.
+ * report[k] belongs to records[k + 1]; returns n_records - 1.
+ * Both checks are enqueued on `stream` and wait for nothing but their own work there, after which
+ * the report is filled (as tk_compare_device_batch).  A null pointer, a wrong dtype, a tensor that
+ * is not compact or a report that is too small: TK_ERR_INVALID_ARG before anything is launched. */
+typedef struct {
+  int32_t node;   /* index in the module's node list */
+  int32_t output; /* index of the node output the op writes (1 .. n_outputs - 1) */
+} tk_chain_op;
+int tk_chain_check_tile(void);
+int tk_module_chain_ops(tk_module* mod, tk_chain_op* ops, int capacity);
+int tk_module_check_chains(tk_module* mod, tk_wire_mismatch* report, int capacity, void* stream);
+int tk_check_chain(int kind, const tk_tensor* const* records, int n_records, const tk_tensor* bias, const void* attrs,
+                   tk_wire_mismatch* report, int capacity, void* stream);
+
 /* Makes `stream` wait for the copies of the last traced run: call before writing any
  * tensor the module reads (GraphModule.set_input / load_params,
  * graph_executor.cc:158-166 SetInput) on a stream of your own. */

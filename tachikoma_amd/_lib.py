@@ -323,6 +323,13 @@ class tk_wire_mismatch(ctypes.Structure):
     ]
 
 
+class tk_chain_op(ctypes.Structure):
+    _fields_ = [
+        ("node", ctypes.c_int32),      # index in the module's node list
+        ("output", ctypes.c_int32),    # index of the node output the tail op writes
+    ]
+
+
 TK_WIRE_UNPACK_STORE, TK_WIRE_UNPACK_COMPARE = 0, 1
 NO_MISMATCH = 0xFFFFFFFFFFFFFFFF
 
@@ -447,6 +454,12 @@ SIGNATURES = {
     "tk_compare_device_batch": (ctypes.c_int, [ctypes.POINTER(_VP), ctypes.POINTER(_VP), ctypes.POINTER(_I64),
                                                ctypes.POINTER(ctypes.c_int32), ctypes.c_int,
                                                ctypes.POINTER(tk_wire_mismatch), _VP]),
+    "tk_chain_check_tile": (ctypes.c_int, []),
+    "tk_module_chain_ops": (ctypes.c_int, [_VP, ctypes.POINTER(tk_chain_op), ctypes.c_int]),
+    "tk_module_check_chains": (ctypes.c_int, [_VP, ctypes.POINTER(tk_wire_mismatch), ctypes.c_int, _VP]),
+    "tk_check_chain": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.POINTER(tk_tensor)), ctypes.c_int,
+                                      ctypes.POINTER(tk_tensor), _VP, ctypes.POINTER(tk_wire_mismatch), ctypes.c_int,
+                                      _VP]),
     "tk_module_tune": (ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32),
                                       ctypes.POINTER(_F32)]),
     "tk_module_set_node_algo": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int]),

@@ -13,7 +13,7 @@ from __future__ import annotations
 import json
 import os
 import time
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Any, Dict, List, Optional, Tuple
 
 import numpy as np
@@ -271,12 +271,28 @@ class VerifyReport:
 
 
 @dataclass
+class FaultyOp:
+    """One op of a replay that did not compute what the file says it did."""
+    name: str                     # the record the op writes
+    op: str                       # the op that produced it
+    node: int                     # index of its node in the native module's node list
+    place: int                    # index in the node's chain of records (0: the head op)
+    count: int                    # differing elements
+    flat_index: int               # the first of them
+    first_index: Tuple[int, ...]  # the same, unravelled
+    basis: str                    # "node": the record differs from what this engine computes from the
+    #                               node's recorded inputs (the replay compare); "input": the record is
+    #                               not the op of its own recorded input (the chain check)
+
+
+@dataclass
 class FaultyNode:
     """One node of a replay with at least one record that differs from the file."""
     node: int                  # index in the native module's node list
     kind: str                  # DeviceModule.node_kinds: "conv_block", "add_block", an op name, ...
     records: Tuple[str, ...]   # the node's records in chain order
     first: str                 # the first of them that differs
+    ops: List[FaultyOp] = field(default_factory=list)  # the faulty ops of the node (ReplayReport.ops)
 
 
 class ReplayReport(VerifyReport):
@@ -285,22 +301,42 @@ class ReplayReport(VerifyReport):
     recorded, not on what the node before it computed, so a fault stays in the node it occurs in
     and an independent fault behind it is reported too.  Graph-input records are loaded, not
     computed, and are never listed.  ``nodes``: one FaultyNode per node with a differing record, in
-    node order; ``first`` is the first faulty node's first differing record.  The granularity is the
-    node: within a fused node (conv -> bias_add -> requantize -> [add] -> [clip]) the ops read one
-    another's values inside one kernel, so a fault still runs down the chain from the op it occurs
-    in.  ``detail(m)`` gives the file's value and the recomputed one (the buffers hold the replayed
-    values).  ``stats`` adds store_ms, shadow_ms, replay_ms (HIP events) and shadows (the number of
-    shadows rebuilt up front) to VerifyReport's."""
+    node order; ``first`` is the first faulty node's first differing record.  ``mismatches`` and
+    ``nodes`` have the granularity of the node: within a fused node (conv -> bias_add -> requantize
+    -> [add] -> [clip]) the ops read one another's values inside one kernel, so in ``mismatches`` a
+    fault still runs down the chain from the op it occurs in.
 
-    def __init__(self, verifier, source, n_records, mismatches, params_differing, stats, nodes):
+    ``ops`` has the granularity of the op: one FaultyOp per faulty op, in trace order (also grouped
+    per node in ``FaultyNode.ops``); without the params, ``ok == (not ops)``.  The head op of a node
+    (conv, dense, the add of an add block; the only op of a pool, a cast or any node of an unfused
+    build) is judged by the replay compare, basis "node".  Every other op of a fused chain is
+    judged by the chain check (tk_module_check_chains), which ran on the file's records before any
+    node did: the op is computed from its own recorded input and compared with its recorded output,
+    basis "input", independently of the op before it (relay/replay.py: attribute_ops).  Consequences:
+    a producer's wrong convolution whose tail is consistent with it is listed as the conv alone,
+    though all of the node's records are in ``mismatches``; a second fault further down the same
+    chain is listed too; a record corrupted in the file is not its op of its input, so it shows as
+    its producer's fault, and, since the next op of the chain read it, possibly as its consumer's
+    (where the corruption changes what the consumer computes) -- a corrupted file and a wrongly
+    computed record cannot be told apart from the file alone.  With ``replay_trace(ops=False)`` the
+    chain check is skipped and ``ops`` is empty.
+
+    ``detail(m)`` gives the file's value and the recomputed one (the buffers hold the replayed
+    values).  ``stats`` adds store_ms, shadow_ms, replay_ms (HIP events), shadows (the number of
+    shadows rebuilt up front) and, with ops, chain_ms (HIP events around the chain check) to
+    VerifyReport's."""
+
+    def __init__(self, verifier, source, n_records, mismatches, params_differing, stats, nodes, ops=()):
         super().__init__(verifier, source, n_records, mismatches, params_differing, stats)
         self.nodes: List[FaultyNode] = nodes
+        self.ops: List[FaultyOp] = list(ops)
         if nodes:
             self.first = next(m for m in mismatches if m.name == nodes[0].first)
 
     def __repr__(self):
         return (f"ReplayReport(ok={self.ok}, n_records={self.n_records}, mismatched={len(self.mismatches)}, "
-                f"faulty_nodes={[n.node for n in self.nodes]}, first={self.first.name if self.first else None}, "
+                f"faulty_nodes={[n.node for n in self.nodes]}, faulty_ops={[o.name for o in self.ops]}, "
+                f"first={self.first.name if self.first else None}, "
                 f"params_equal={self.params_equal})")
 
 
@@ -827,7 +863,7 @@ class GraphModule:
         stats["compare_ms"] = (time.perf_counter() - t1) * 1e3
         return VerifyReport(v, path_or_bytes, len(ct.entries), v.mismatches(ct, found), params_differing, stats)
 
-    def replay_trace(self, path_or_bytes) -> ReplayReport:
+    def replay_trace(self, path_or_bytes, ops: bool = True) -> ReplayReport:
         """Re-execute every op of a trace file from its recorded inputs and compare, on the device.
         Reading, the host checks and the upload are verify_trace's (a damaged file is a ValueError
         before anything reaches the device).  Then every record of the file is stored into the
@@ -835,7 +871,9 @@ class GraphModule:
         one launch (tk_conv2d_make_shadow_batch), the nodes run in the order of relay/replay.py
         (record-producing nodes in reverse, each after the helper nodes it needs:
         tk_module_run_order), and one compare pass over the whole file gives the verdict of every
-        node at once (ReplayReport).  The nodes compute with the module's own params and packed
+        node at once (ReplayReport).  With ``ops`` the chain check (tk_module_check_chains) runs
+        between the store pass and the node run, where the buffers hold the file's records, and the
+        report lists the faulty ops (ReplayReport.ops).  The nodes compute with the module's own params and packed
         weights; the file's params are compared and reported as by verify_trace.  Afterwards the
         buffers hold the replayed values, not a run's: the next run() overwrites everything."""
         import torch
@@ -849,6 +887,13 @@ class GraphModule:
         ev[0].record(stream)
         v.store(ct, {e.name for e in ct.entries}, stream)
         ev[1].record(stream)
+        chain = None
+        if ops:
+            ce = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ce[0].record(stream)
+            chain = self.module.check_chains(stream)
+            ce[1].record(stream)
+            ev[1] = ce[1]
         self.module.rebuild_shadows(shadows, stream)
         ev[2].record(stream)
         self.module.run_order(order, stream)
@@ -856,7 +901,10 @@ class GraphModule:
         stream.synchronize()
         t1 = time.perf_counter()
         found, params_differing = v.compare(ct, stream)
-        stats["store_ms"], stats["shadow_ms"], stats["replay_ms"] = (ev[k].elapsed_time(ev[k + 1]) for k in range(3))
+        stats["shadow_ms"], stats["replay_ms"] = (ev[k].elapsed_time(ev[k + 1]) for k in (1, 2))
+        stats["store_ms"] = ev[0].elapsed_time(ce[0] if ops else ev[1])
+        if ops:
+            stats["chain_ms"] = ce[0].elapsed_time(ce[1])
         stats["shadows"] = len(shadows)
         stats["run_ms"] = (t1 - t0) * 1e3
         stats["compare_ms"] = (time.perf_counter() - t1) * 1e3
@@ -867,7 +915,23 @@ class GraphModule:
         bad = {m.name for m in mismatches}
         nodes = [FaultyNode(i, self.module.node_kinds[i], tuple(recs), next(r for r in recs if r in bad))
                  for i, recs in enumerate(self.module.node_records) if any(r in bad for r in recs)]
-        return ReplayReport(v, path_or_bytes, len(ct.entries), mismatches, params_differing, stats, nodes)
+        faulty = []
+        if ops:
+            from ..relay.replay import attribute_ops
+            shapes = {e.name: e.shape for e in ct.entries}
+            for o in attribute_ops([(i, recs) for i, recs in enumerate(self.module.node_records) if recs],
+                                   {m.name: (m.count, m.flat_index) for m in mismatches}, chain):
+                shape = shapes[o["name"]]
+                idx = tuple(int(i) for i in np.unravel_index(o["first"], shape)) if shape else ()
+                faulty.append(FaultyOp(o["name"], v.ops.get(o["name"], "?"), o["node"], o["place"], o["count"],
+                                       o["first"], idx, o["basis"]))
+            position = {e.name: k for k, e in enumerate(ct.entries)}
+            faulty.sort(key=lambda o: position[o.name])
+            by_node = {n.node: n for n in nodes}
+            for o in faulty:
+                if o.node in by_node:
+                    by_node[o.node].ops.append(o)
+        return ReplayReport(v, path_or_bytes, len(ct.entries), mismatches, params_differing, stats, nodes, faulty)
 
     def load_trace(self, path_or_bytes, shadows: bool = False) -> None:
         """Put a trace file's records into the module's record buffers (the reading and the checks

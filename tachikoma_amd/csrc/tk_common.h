@@ -165,4 +165,36 @@ __device__ __forceinline__ int32_t rq_apply(int32_t t, int c, const RqParams& p)
   return t;
 }
 
+// ---------------------------------------------------------------- mismatch reports (device)
+// Workgroup-wide sum of `cnt` and minimum of `first` into *out; every thread of the 256 calls it.
+// The atomics are issued by one thread, and only if some thread counted a mismatch.
+__device__ __forceinline__ void wire_report_mismatches(uint32_t cnt, unsigned long long first, tk_wire_mismatch* out,
+                                                       uint32_t* s_any, unsigned long long* s_red) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const bool mine = __any(cnt != 0);
+  if (lane == 0) s_any[wave] = mine;
+  __syncthreads();
+  if (s_any[0] | s_any[1] | s_any[2] | s_any[3]) {  // the same for the whole workgroup
+    unsigned long long c = cnt, f = first;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+      c += __shfl_xor(c, m, 64);
+      const unsigned long long o = __shfl_xor(f, m, 64);
+      f = o < f ? o : f;
+    }
+    if (lane == 0) s_red[wave] = c, s_red[4 + wave] = f;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      unsigned long long total = 0, lowest = ~0ull;
+      for (int w = 0; w < 4; ++w) total += s_red[w], lowest = s_red[4 + w] < lowest ? s_red[4 + w] : lowest;
+      atomicAdd(reinterpret_cast<unsigned long long*>(&out->mismatches), total);
+      atomicMin(reinterpret_cast<unsigned long long*>(&out->first), lowest);
+    }
+  }
+  __syncthreads();  // s_any / s_red are reused by the next record
+}
+
+// Resets `report` (device, n entries) on `s`: no mismatch, first = ~0 (tk_trace.hip).
+int wire_report_init(tk_wire_mismatch* report, int n, hipStream_t s);
+
 }  // namespace tk

@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "tk_chain.h"
 #include "tk_common.h"
 #include "tk_wire.h"
 
@@ -372,6 +373,16 @@ struct tk_module {
   bool wire_tail_used = false;
   std::atomic<int> wire_failed{0};
   PackPlan* last_wire_plan = nullptr;
+  // chain check (tk_module_check_chains): the table of the module's fused chains, laid out on the
+  // first call and kept on the device with its report, so later calls upload nothing
+  struct Chains {
+    bool built = false;
+    std::vector<tk_chain_op> ops;  // one per report entry: node order, then chain order
+    int n_chains = 0;
+    int64_t blocks = 0;
+    void* dev = nullptr;  // ChainDev[n_chains] | tk_wire_mismatch[ops.size()]
+    tk_wire_mismatch* report = nullptr;
+  } chains;
   void drop_graph() {
     last_wire_plan = nullptr;
     for (Graph& x : graphs) {
@@ -384,6 +395,7 @@ struct tk_module {
   }
   ~tk_module() {
     drop_graph();
+    if (chains.dev) (void)hipFree(chains.dev);
     for (auto e : done) (void)hipEventDestroy(e);
     for (auto e : prof) (void)hipEventDestroy(e);
     if (capture_done) (void)hipEventDestroy(capture_done);
@@ -1344,6 +1356,91 @@ int tk_module_run_order(tk_module* mod, const int32_t* order, int n, void* strea
     if (rc) return rc;
   }
   return TK_OK;
+}
+
+// Lays out the chain table of the module's conv, dense and add blocks and puts it on the device.
+static int build_chains(tk_module* mod, hipStream_t s) {
+  tk_module::Chains& c = mod->chains;
+  std::vector<tk::ChainDev> table;
+  std::vector<tk_chain_op> ops;
+  int n_report = 0;
+  int64_t blocks = 0;
+  for (size_t i = 0; i < mod->nodes.size(); ++i) {
+    tk::Node& n = mod->nodes[i];
+    const tk_node& d = n.desc;
+    if (d.kind != TK_NODE_CONV_BLOCK && d.kind != TK_NODE_DENSE_BLOCK && d.kind != TK_NODE_ADD_BLOCK) continue;
+    tk::ChainSpec sp{};
+    sp.kind = d.kind;
+    sp.outs = n.outp;
+    sp.n_outs = d.n_outputs;
+    if (d.kind == TK_NODE_ADD_BLOCK) {
+      sp.add_block = &d.attrs.add_block;
+    } else {
+      sp.bias = &n.in[2].t;
+      sp.block = &d.attrs.block;
+      if (d.attrs.block.has_add) sp.residual = &n.in[3].t;
+    }
+    const int before = n_report;
+    if (const int rc = tk::chain_append(sp, "tk_module_check_chains", &table, &n_report, &blocks)) return rc;
+    // the tail ops write outputs 1 .. n_outputs - 1 of the node, in chain order
+    for (int k = 0; k < n_report - before; ++k) ops.push_back({(int32_t)i, d.n_outputs - (n_report - before) + k});
+  }
+  if (blocks >= ((int64_t)1 << 31)) {
+    tk::set_error("tk_module_check_chains: too much to check in one launch");
+    return TK_ERR_UNSUPPORTED;
+  }
+  if (!table.empty()) {
+    const int64_t table_bytes = tk::wire_align((int64_t)(table.size() * sizeof(tk::ChainDev)), 64);
+    TK_HIP(hipMalloc(&c.dev, (size_t)(table_bytes + n_report * (int64_t)sizeof(tk_wire_mismatch))));
+    c.report = (tk_wire_mismatch*)((char*)c.dev + table_bytes);
+    // once per module: wait, so that the table is there whichever stream a later call uses
+    TK_HIP(hipMemcpyAsync(c.dev, table.data(), table.size() * sizeof(tk::ChainDev), hipMemcpyHostToDevice, s));
+    TK_HIP(hipStreamSynchronize(s));
+  }
+  c.n_chains = (int)table.size();
+  c.blocks = blocks;
+  c.ops = std::move(ops);
+  c.built = true;
+  return TK_OK;
+}
+
+int tk_module_chain_ops(tk_module* mod, tk_chain_op* ops, int capacity) {
+  if (!mod || capacity < 0 || (capacity > 0 && !ops)) {
+    tk::set_error("tk_module_chain_ops: null module or null array");
+    return TK_ERR_INVALID_ARG;
+  }
+  if (!mod->chains.built)
+    if (const int rc = build_chains(mod, nullptr)) return rc;
+  const int n = (int)mod->chains.ops.size();
+  for (int k = 0; k < std::min(n, capacity); ++k) ops[k] = mod->chains.ops[k];
+  return n;
+}
+
+int tk_module_check_chains(tk_module* mod, tk_wire_mismatch* report, int capacity, void* stream) {
+  if (!mod || !report || capacity < 0) {
+    tk::set_error("tk_module_check_chains: null module or null report");
+    return TK_ERR_INVALID_ARG;
+  }
+  hipStream_t s = tk::as_stream(stream);
+  tk_module::Chains& c = mod->chains;
+  if (!c.built)
+    if (const int rc = build_chains(mod, s)) return rc;
+  const int n = (int)c.ops.size();
+  if (n > capacity) {
+    tk::set_error("tk_module_check_chains: the report holds " + std::to_string(capacity) + " entries, the module has " +
+                  std::to_string(n) + " tail ops (tk_module_chain_ops)");
+    return TK_ERR_INVALID_ARG;
+  }
+  for (int k = 0; k < n; ++k) report[k].mismatches = 0, report[k].first = ~(uint64_t)0;
+  if (c.n_chains == 0) return n;
+  if (const int rc = tk::chain_check_impl((const tk::ChainDev*)c.dev, c.n_chains, c.blocks, c.report, n, s)) return rc;
+  TK_HIP(hipMemcpyAsync(report, c.report, (size_t)n * sizeof(tk_wire_mismatch), hipMemcpyDeviceToHost, s));
+  // the report is filled once the call's own work on `stream` is complete, as tk_compare_device_batch's
+  if (hipStreamSynchronize(s) != hipSuccess) {
+    tk::set_error("tk_module_check_chains: the chain-check kernel failed");
+    return TK_ERR_HIP;
+  }
+  return n;
 }
 
 int tk_module_run_profiled(tk_module* mod, void* stream, float* node_ms) {

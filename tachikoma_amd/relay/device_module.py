@@ -962,6 +962,30 @@ class DeviceModule:
                    "tk_conv2d_make_shadow_batch")
         return len(names)
 
+    def chain_ops(self) -> List[str]:
+        """The records of the tail ops the chain check judges, in report order (node order, then
+        chain order): every record of a conv, dense or add block but its first
+        (tk_module_chain_ops), computed once."""
+        if getattr(self, "_chain_ops", None) is None:
+            n = self.lib.tk_module_chain_ops(self.handle, None, 0)
+            _lib.check(min(n, 0), "tk_module_chain_ops")
+            ops = (_lib.tk_chain_op * max(1, n))()
+            _lib.check(min(self.lib.tk_module_chain_ops(self.handle, ops, n), 0), "tk_module_chain_ops")
+            self._chain_ops = [self.node_records[ops[k].node][ops[k].output] for k in range(n)]
+            self._chain_report = (_lib.tk_wire_mismatch * max(1, n))()
+        return self._chain_ops
+
+    def check_chains(self, stream=None) -> Dict[str, tuple]:
+        """The chain check on the record buffers as they stand (tk_module_check_chains; after
+        load_trace they hold a file's records): {tail record: (count, first flat index)} -- how many
+        elements of the record are not its op of its own recorded input, and the first of them
+        (_lib.NO_MISMATCH if none).  One launch; returns when it has completed on ``stream``."""
+        names = self.chain_ops()
+        n = self.lib.tk_module_check_chains(self.handle, self._chain_report, len(names),
+                                            ctypes.c_void_p(_lib.stream_handle(stream)))
+        _lib.check(min(n, 0), "tk_module_check_chains")
+        return {name: (int(r.mismatches), int(r.first)) for name, r in zip(names, self._chain_report)}
+
     def run_profiled(self, stream=None) -> Dict[str, float]:
         ms = (ctypes.c_float * self.n_nodes)()
         _lib.check(self.lib.tk_module_run_profiled(self.handle, ctypes.c_void_p(_lib.stream_handle(stream)), ms),

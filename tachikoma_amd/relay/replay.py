@@ -1,5 +1,6 @@
-"""The schedule of a trace replay (GraphModule.replay_trace): pure host logic over the plain data
-DeviceModule keeps while it emits nodes.  Imports nothing but the standard library.
+"""The schedule of a trace replay (GraphModule.replay_trace) and the attribution of its findings to
+ops (attribute_ops, at the end): pure host logic over the plain data DeviceModule keeps while it
+emits nodes.  Imports nothing but the standard library.
 
 ``node_io[k]`` describes node k of the native module::
 
@@ -28,7 +29,7 @@ non-record tensor is rebuilt by the helpers of the unit that reads it.
 """
 from __future__ import annotations
 
-from typing import Dict, Iterable, List, Sequence, Tuple
+from typing import Dict, Iterable, List, Mapping, Optional, Sequence, Tuple
 
 
 class UnsupportedError(NotImplementedError):
@@ -84,3 +85,55 @@ def replay_order(node_io: Sequence[dict], inputs: Iterable[str] = ()) -> Tuple[L
     before it and no up-front rebuild produces."""
     units, upfront = replay_units(node_io, inputs)
     return [i for u in reversed(units) for i in u], upfront
+
+
+def attribute_ops(nodes: Sequence[Tuple[int, Sequence[str]]], mismatches: Mapping[str, Tuple[int, int]],
+                  chain: Optional[Mapping[str, Tuple[int, int]]] = None) -> List[dict]:
+    """One verdict per op from the two checks of a replay.
+
+    ``nodes``: (node index, its records in chain order) of every record-producing node, in node
+    order.  ``mismatches``: {record: (count, first flat index)} of the replay compare -- the record
+    differs from what this engine computes from the recorded inputs of its *node*; records that are
+    equal may be left out or carry a count of 0; names that are no node's record (graph inputs) are
+    ignored.  ``chain``: {record: (count, first)} of the chain check -- the tail record is not the op
+    of its own recorded *input*; it holds every tail record that was checked, equal ones with a
+    count of 0.  None: no chain check was made.
+
+    Returns the faulty ops in node order, then chain order, each as
+    {"name", "node", "place" (index in the chain), "basis", "count", "first"}:
+
+    - the head op of a node (place 0; the only op of an unfused node) is faulty when its record
+      differs in the replay: basis "node";
+    - a tail op the chain check covers is faulty when the chain check says so, whatever the replay
+      says of its record: basis "input".  A producer's fault that the tail carries on consistently
+      is therefore the producer's alone, and a second fault further down the chain is found;
+    - where the chain check does not cover a node's tail, the node keeps node granularity: its
+      first differing record stands for it, basis "node"."""
+    out: List[dict] = []
+
+    def bad(table, name):
+        c = table.get(name)
+        return c if c is not None and c[0] else None
+
+    for node, records in nodes:
+        records = list(records)
+        if not records:
+            continue
+        tail = records[1:]
+        covered = chain is not None and all(r in chain for r in tail)
+        if covered:
+            head = bad(mismatches, records[0])
+            if head:
+                out.append({"name": records[0], "node": node, "place": 0, "basis": "node", "count": head[0],
+                            "first": head[1]})
+            for k, r in enumerate(tail, 1):
+                c = bad(chain, r)
+                if c:
+                    out.append({"name": r, "node": node, "place": k, "basis": "input", "count": c[0], "first": c[1]})
+        else:
+            for k, r in enumerate(records):
+                c = bad(mismatches, r)
+                if c:
+                    out.append({"name": r, "node": node, "place": k, "basis": "node", "count": c[0], "first": c[1]})
+                    break
+    return out

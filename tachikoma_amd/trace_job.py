@@ -31,7 +31,7 @@ CLI (one process per GPU, torch.distributed.run environment; rank 0 writes the m
 engine on the device, record by record (:func:`check`, GraphModule.verify_trace), printing one JSON
 line per chunk; ``--verify`` keeps its meaning (re-digest the files a resumed job keeps).  ``--check
 --replay`` re-executes every op of each chunk from its recorded inputs instead
-(GraphModule.replay_trace) and adds the faulty nodes to the chunk's JSON line.
+(GraphModule.replay_trace) and adds the faulty nodes and the faulty ops to the chunk's JSON line.
 """
 from __future__ import annotations
 
@@ -323,7 +323,8 @@ def check(tracer: GraphModuleTracer, out_dir: str, rank: int = 0, stem: str = "t
     {name, op, first_index} | None, "params_equal", **stats}.  A missing or unreadable file, or one
     that does not parse or is of another graph, is ``ok: False`` with ``"error"``.  With ``replay``
     each chunk is replayed op by op from its recorded inputs instead (GraphModule.replay_trace) and
-    the dict also has "nodes": [{node, kind, records, first}] of the faulty nodes."""
+    the dict also has "nodes": [{node, kind, records, first}] of the faulty nodes and "ops": [{name,
+    op, node, place, basis, count, first_index}] of the faulty ops (ReplayReport.ops)."""
     out = []
     for index, e in sorted(Journal(journal_file(out_dir, rank, stem)).entries().items()):
         row = {"chunk": index, "file": e.get("file")}
@@ -340,6 +341,8 @@ def check(tracer: GraphModuleTracer, out_dir: str, rank: int = 0, stem: str = "t
             if replay:
                 row["nodes"] = [{"node": n.node, "kind": n.kind, "records": list(n.records), "first": n.first}
                                 for n in rep.nodes]
+                row["ops"] = [{"name": o.name, "op": o.op, "node": o.node, "place": o.place, "basis": o.basis,
+                               "count": o.count, "first_index": list(o.first_index)} for o in rep.ops]
         if log:
             log(f"rank {rank}: chunk {index} {'ok' if row['ok'] else 'FAILED'}")
         out.append(row)
