@@ -837,6 +837,57 @@ int tk_module_check_chains(tk_module* mod, tk_wire_mismatch* report, int capacit
 int tk_check_chain(int kind, const tk_tensor* const* records, int n_records, const tk_tensor* bias, const void* attrs,
                    tk_wire_mismatch* report, int capacity, void* stream);
 
+/* Per-record statistics: value ranges and bit widths without moving the trace.
+ *
+ * What Trace.calibrate's users reduce every record to on the host, computed where the records lie:
+ * one launch reduces n records to exact integer statistics and merges them into n device-resident
+ * tk_record_stats entries, so a dataset is calibrated run after run with no record leaving the
+ * device and no host synchronisation.  Element kinds are tk_wire_record's: 0 int32, 1 int8,
+ * 2 uint8.  Fields, accumulated over every run since the last reset: `count` elements; `sum` of
+ * them modulo 2^64; `min` / `max` (INT32_MAX / INT32_MIN while count == 0); bits[b], the number of
+ * elements whose magnitude has bit length b (b(0) = 0, b(x) = floor(log2|x|) + 1, so INT32_MIN
+ * gives 32); values[v - dtype_min], the number of elements equal to v, for the 1-byte kinds only
+ * (int8 is indexed by v + 128, uint8 by v; all zero for int32).
+ *
+ * A workgroup takes tk_record_stats_span() consecutive elements of one record -- a whole number of
+ * tiles of tk_record_stats_tile() elements; a record of more than 512 spans is cut into 512 runs of
+ * a whole number of spans instead, since all workgroups of a record flush into one entry -- a lane
+ * 16 bytes at a time where the record's buffer
+ * is 16-byte aligned (element by element at a ragged end and in a buffer that is not; a 1-byte
+ * buffer may have any alignment, an int32 one must be 4-byte aligned), every byte read once.  min,
+ * max and sum are kept in registers, the histograms in LDS; a workgroup flushes once, with integer
+ * atomics on the non-zero bins only, so the result does not depend on arrival order and is equal
+ * on every run.
+ *
+ * tk_stats_plan_create: lays out the job table of n records (src[i]: device buffer, n_elems[i]
+ * elements of kinds[i]) and uploads it once; the plan owns it.  A record of no elements is allowed
+ * and its entry is never touched.  tk_record_stats_reset: writes the identity into n entries
+ * (device memory, 8-byte aligned).  tk_stats_plan_run: exactly one launch on `stream` that merges
+ * the records as they stand into stats_dev[0..n); uploads nothing, synchronises nothing.  Several
+ * plans may merge into one array.  tk_record_stats_batch: the one-shot form -- plan, reset, run,
+ * copy into out_host (n entries), synchronise `stream`, destroy.
+ * Refused before any launch: a null argument, n <= 0, a negative count, an int32 buffer that is
+ * not 4-byte aligned or more workgroups than one launch takes (TK_ERR_INVALID_ARG); a kind outside
+ * 0..2 (TK_ERR_UNSUPPORTED). */
+typedef struct {
+  uint64_t count;
+  int64_t sum;
+  int32_t min, max;
+  uint64_t bits[33];
+  uint64_t values[256];
+} tk_record_stats;
+typedef struct tk_stats_plan tk_stats_plan;
+int tk_record_stats_tile(void);
+int tk_record_stats_span(void);
+int tk_record_stats_size(void); /* sizeof(tk_record_stats), for the binding */
+int tk_stats_plan_create(const void* const* src, const int64_t* n_elems, const int32_t* kinds, int n,
+                         tk_stats_plan** out);
+int tk_stats_plan_destroy(tk_stats_plan* plan);
+int tk_record_stats_reset(tk_record_stats* stats_dev, int n, void* stream);
+int tk_stats_plan_run(tk_stats_plan* plan, tk_record_stats* stats_dev, void* stream);
+int tk_record_stats_batch(const void* const* src, const int64_t* n_elems, const int32_t* kinds, int n,
+                          tk_record_stats* out_host, void* stream);
+
 /* Makes `stream` wait for the copies of the last traced run: call before writing any
  * tensor the module reads (GraphModule.set_input / load_params,
  * graph_executor.cc:158-166 SetInput) on a stream of your own. */

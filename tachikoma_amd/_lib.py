@@ -330,6 +330,17 @@ class tk_chain_op(ctypes.Structure):
     ]
 
 
+class tk_record_stats(ctypes.Structure):
+    _fields_ = [
+        ("count", ctypes.c_uint64),
+        ("sum", ctypes.c_int64),       # modulo 2^64
+        ("min", ctypes.c_int32),       # INT32_MAX while count == 0
+        ("max", ctypes.c_int32),       # INT32_MIN while count == 0
+        ("bits", ctypes.c_uint64 * 33),     # by bit length of the magnitude
+        ("values", ctypes.c_uint64 * 256),  # 1-byte kinds: by v - dtype_min
+    ]
+
+
 TK_WIRE_UNPACK_STORE, TK_WIRE_UNPACK_COMPARE = 0, 1
 NO_MISMATCH = 0xFFFFFFFFFFFFFFFF
 
@@ -460,6 +471,16 @@ SIGNATURES = {
     "tk_check_chain": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.POINTER(tk_tensor)), ctypes.c_int,
                                       ctypes.POINTER(tk_tensor), _VP, ctypes.POINTER(tk_wire_mismatch), ctypes.c_int,
                                       _VP]),
+    "tk_record_stats_tile": (ctypes.c_int, []),
+    "tk_record_stats_span": (ctypes.c_int, []),
+    "tk_record_stats_size": (ctypes.c_int, []),
+    "tk_stats_plan_create": (ctypes.c_int, [ctypes.POINTER(_VP), ctypes.POINTER(_I64), ctypes.POINTER(ctypes.c_int32),
+                                            ctypes.c_int, ctypes.POINTER(_VP)]),
+    "tk_stats_plan_destroy": (ctypes.c_int, [_VP]),
+    "tk_record_stats_reset": (ctypes.c_int, [_VP, ctypes.c_int, _VP]),
+    "tk_stats_plan_run": (ctypes.c_int, [_VP, _VP, _VP]),
+    "tk_record_stats_batch": (ctypes.c_int, [ctypes.POINTER(_VP), ctypes.POINTER(_I64), ctypes.POINTER(ctypes.c_int32),
+                                             ctypes.c_int, _VP, _VP]),
     "tk_module_tune": (ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32),
                                       ctypes.POINTER(_F32)]),
     "tk_module_set_node_algo": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int]),

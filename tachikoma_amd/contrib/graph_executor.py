@@ -10,6 +10,7 @@ executor's per-node dump (python/tvm/contrib/debugger/debug_executor.py:210-347)
 """
 from __future__ import annotations
 
+import ctypes
 import json
 import os
 import time
@@ -508,6 +509,76 @@ class TraceVerifier:
         return out
 
 
+class StatsAccumulator:
+    """Per-record statistics accumulated on the device (tk_stats_plan_run into device-resident
+    tk_record_stats entries): ``add`` after each run merges the record buffers as they stand,
+    with no synchronisation, so ``for batch in data: gm.run(**batch); acc.add()`` calibrates over
+    a dataset without a record leaving the device.  ``result`` copies the entries out and
+    synchronises.  ``skipped`` names the records whose dtype the kernel does not cover.  The
+    device memory is released by ``close`` or when the module is closed."""
+
+    def __init__(self, module: DeviceModule, plan):
+        import torch
+        self.module, self.plan = module, plan
+        self.names, self.skipped = list(plan.names), list(plan.skipped)
+        words = max(1, len(self.names)) * tf.STATS_DTYPE.itemsize // 8
+        self._dev = torch.empty(words, dtype=torch.int64, device=module.device)
+        self._host = torch.empty(words, dtype=torch.int64, pin_memory=True)
+        self.reset()
+
+    def _stream(self, stream=None):
+        import torch
+        return torch.cuda.current_stream(self.module.device) if stream is None else stream
+
+    def _live(self) -> None:
+        if self._dev is None or self.module.closed:
+            raise _lib.TachikomaError("the statistics accumulator was closed (with its module)")
+
+    def reset(self, stream=None) -> None:
+        """Back to the identity (no elements), enqueued on the stream."""
+        self._live()
+        if self.names:
+            _lib.check(self.module.lib.tk_record_stats_reset(
+                ctypes.c_void_p(self._dev.data_ptr()), len(self.names),
+                ctypes.c_void_p(_lib.stream_handle(self._stream(stream)))), "tk_record_stats_reset")
+
+    def add(self, stream=None) -> None:
+        """Merge the record buffers as they stand: one launch on ``stream`` (default: the current
+        one, where the run was enqueued), nothing uploaded, nothing waited for."""
+        self._live()
+        if self.names:
+            _lib.check(self.module.lib.tk_stats_plan_run(
+                self.plan.handle, ctypes.c_void_p(self._dev.data_ptr()),
+                ctypes.c_void_p(_lib.stream_handle(self._stream(stream)))), "tk_stats_plan_run")
+
+    def copy_to(self, host, stream=None) -> None:
+        """Enqueue the copy of the entries into ``host`` (a pinned int64 tensor of ``words``)."""
+        import torch
+        self._live()
+        with torch.cuda.stream(self._stream(stream)):
+            host.copy_(self._dev, non_blocking=True)
+
+    @property
+    def words(self) -> int:
+        return int(self._host.numel())
+
+    def decode(self, host) -> Dict[str, "tf.RecordStats"]:
+        rows = host.numpy().view(tf.STATS_DTYPE)
+        return {n: tf.RecordStats.from_struct(rows[i], d, n)
+                for i, (n, d) in enumerate(zip(self.names, self.plan.dtypes))}
+
+    def result(self, stream=None) -> Dict[str, "tf.RecordStats"]:
+        """{name: RecordStats} of everything added since the last reset: one copy, one
+        synchronisation."""
+        s = self._stream(stream)
+        self.copy_to(self._host, s)
+        s.synchronize()
+        return self.decode(self._host)
+
+    def close(self) -> None:
+        self._dev = None
+
+
 class BenchmarkResult:
     """Runtimes from benchmarking, in seconds (python/tvm/runtime/module.py:34-98): ``results``
     and their mean / std / median / min / max."""
@@ -582,6 +653,8 @@ class GraphModule:
         self._capture: Optional[TraceCapture] = None
         self._packed: Optional[PackedCapture] = None
         self._verifier: Optional[TraceVerifier] = None
+        self._accumulators: List[StatsAccumulator] = []
+        self._one_shot: Dict[tuple, StatsAccumulator] = {}
         self._meta = {"format": "tachikoma-trace", "version": tf.TRACE_VERSION, "model": "graph",
                       "target": "mi355x", "sample_offset": 0, "rank": 0, "world": 1,
                       "semantics": {"reference": "tvm llvm target without -mcpu", "requantize_compute_dtype":
@@ -598,6 +671,9 @@ class GraphModule:
         (or use the module as a context manager) before the process exits; an atexit hook closes
         any module left open (device_module.close_all)."""
         self.module.close()
+        for acc in self._accumulators:
+            acc.close()
+        self._accumulators, self._one_shot = [], {}
         if self._capture is not None:
             self._capture.capture_stream.synchronize()
             self._capture = None
@@ -950,6 +1026,27 @@ class GraphModule:
         if shadows:
             self.module.rebuild_shadows(None, stream)
         stream.synchronize()
+
+    def stats_accumulator(self, names=None) -> StatsAccumulator:
+        """A fresh accumulator over the records ``names`` (default: all of them): ``add()`` after
+        each run, ``result()`` at the end (StatsAccumulator).  Its device memory lives until it or
+        this module is closed."""
+        acc = StatsAccumulator(self.module, self.module.stats_plan(names))
+        self._accumulators.append(acc)
+        return acc
+
+    def record_stats(self, names=None) -> Dict[str, "tf.RecordStats"]:
+        """{name: RecordStats} of the record buffers as they stand -- after run, load_trace or a
+        replay -- computed on the device: one statistics launch, one copy, one synchronisation.
+        Records of dtypes the kernel does not cover are left out (stats_accumulator(...).skipped
+        lists them).  Equals trace_format.record_stats of each record's host copy."""
+        key = None if names is None else tuple(names)
+        acc = self._one_shot.get(key)
+        if acc is None:
+            acc = self._one_shot[key] = self.stats_accumulator(names)
+        acc.reset()
+        acc.add()
+        return acc.result()
 
     def trace_digest(self) -> int:
         """u64 digest of the last run's records, computed on the device

@@ -837,6 +837,7 @@ class DeviceModule:
         finally:
             self.handle = None
             _LIVE.discard(self)
+            self._destroy_stats_plans()  # their job tables point into the record buffers
             _lib.check(self.lib.tk_module_destroy(h), "tk_module_destroy")
             self.buffers = {}
             self._keep = []
@@ -1144,8 +1145,47 @@ class DeviceModule:
                                             ctypes.c_void_p(self._digest_out.data_ptr()), s), "digest")
         return self._digest_out
 
+    def stats_plan(self, names=None) -> "StatsPlan":
+        """The statistics plan (tk_stats_plan) over the record buffers ``names`` (default: every
+        record of plan.records, in trace order), built once per name tuple and kept until close().
+        Records whose dtype the kernel does not cover are left out and listed in ``skipped``."""
+        from ..trace_format import STATS_KIND
+        recs = {t.name: t for t in self.plan.records}
+        key = tuple(recs) if names is None else tuple(names)
+        plans = self.__dict__.setdefault("_stats_plans", {})
+        if key not in plans:
+            for name in key:
+                if name not in recs:
+                    raise KeyError(f"stats_plan: {name} is not a record of the graph")
+            taken = [n for n in key if str(recs[n].dtype) in STATS_KIND]
+            skipped = [n for n in key if str(recs[n].dtype) not in STATS_KIND]
+            handle = ctypes.c_void_p()
+            if taken:
+                n = len(taken)
+                src = (ctypes.c_void_p * n)(*[self.buffers[k].data_ptr() for k in taken])
+                counts = (ctypes.c_int64 * n)(*[self.buffers[k].numel() for k in taken])
+                kinds = (ctypes.c_int32 * n)(*[STATS_KIND[str(recs[k].dtype)] for k in taken])
+                _lib.check(self.lib.tk_stats_plan_create(src, counts, kinds, n, ctypes.byref(handle)),
+                           "tk_stats_plan_create")
+            plans[key] = StatsPlan(handle, taken, [str(recs[k].dtype) for k in taken], skipped)
+        return plans[key]
+
+    def _destroy_stats_plans(self) -> None:
+        for p in self.__dict__.pop("_stats_plans", {}).values():
+            if p.handle:
+                self.lib.tk_stats_plan_destroy(p.handle)
+                p.handle = ctypes.c_void_p()
+
     def output(self, name: str):
         return self.buffers[name]
+
+
+class StatsPlan:
+    """A native statistics plan and what it covers: ``names`` / ``dtypes`` of the records it
+    reduces, in the order of the stats array's entries, and the ``skipped`` names."""
+
+    def __init__(self, handle, names, dtypes, skipped):
+        self.handle, self.names, self.dtypes, self.skipped = handle, list(names), list(dtypes), list(skipped)
 
 
 def _fill_qnn_add(qa, a) -> None:

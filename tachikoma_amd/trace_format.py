@@ -646,6 +646,167 @@ def packed_info(path_or_bytes) -> Dict[str, Any]:
                       "coding": "raw" if e.coding == RAW else e.coding, "diff": e.diff} for e in pf.entries]}
 
 
+# ---------------------------------------------------------------- per-record statistics
+# Host twin of the device statistics (tk_record_stats, csrc/tk_stats.hip): what a calibration
+# reduces a record to -- count, sum, min, max, the histogram of magnitude bit lengths and, for
+# 1-byte records, the histogram of values.  Everything is an exact integer, so the device's
+# result, a trace file's and a merge of either are equal, not close.
+
+STATS_KIND = WIRE_KIND  # the dtypes the statistics cover, by element kind
+STATS_BITS, STATS_VALUES = 33, 256
+STATS_DTYPE = np.dtype([("count", "<u8"), ("sum", "<i8"), ("min", "<i4"), ("max", "<i4"),
+                        ("bits", "<u8", (STATS_BITS,)), ("values", "<u8", (STATS_VALUES,))])
+_I32_MAX, _I32_MIN = 2 ** 31 - 1, -2 ** 31
+
+
+def _wrap_i64(x: int) -> int:
+    return (int(x) + 2 ** 63) % 2 ** 64 - 2 ** 63
+
+
+@dataclass
+class RecordStats:
+    """Statistics of one record over everything accumulated into it.  ``sum`` is modulo 2^64 (as
+    ``np.sum(x, dtype=np.int64)`` wraps); while ``count == 0``, ``min`` / ``max`` are INT32_MAX /
+    INT32_MIN.  ``bits[b]`` counts the elements whose magnitude has bit length b (0 for 0, 32 for
+    INT32_MIN); ``values[v - dtype_min]`` counts the elements equal to v (1-byte dtypes; None for
+    int32)."""
+    name: str
+    dtype: str
+    count: int
+    min: int
+    max: int
+    sum: int
+    bits: np.ndarray
+    values: Optional[np.ndarray]
+
+    @staticmethod
+    def empty(dtype: str, name: str = "") -> "RecordStats":
+        dtype = str(np.dtype(dtype))
+        if dtype not in STATS_KIND:
+            raise ValueError(f"record statistics cover {sorted(STATS_KIND)}, not {dtype}")
+        return RecordStats(name, dtype, 0, _I32_MAX, _I32_MIN, 0, np.zeros(STATS_BITS, np.uint64),
+                           None if dtype == "int32" else np.zeros(STATS_VALUES, np.uint64))
+
+    @staticmethod
+    def from_struct(row, dtype: str, name: str = "") -> "RecordStats":
+        """From one tk_record_stats entry (an element of a STATS_DTYPE array)."""
+        dtype = str(np.dtype(dtype))
+        return RecordStats(name, dtype, int(row["count"]), int(row["min"]), int(row["max"]), int(row["sum"]),
+                           np.array(row["bits"], np.uint64),
+                           None if dtype == "int32" else np.array(row["values"], np.uint64))
+
+    @property
+    def absmax(self) -> int:
+        """Largest magnitude, a Python int (2^31 for INT32_MIN); 0 for no elements."""
+        return max(abs(self.min), abs(self.max)) if self.count else 0
+
+    @property
+    def mean(self) -> float:
+        return self.sum / self.count if self.count else float("nan")
+
+    def bit_width(self, coverage: float = 1.0) -> int:
+        """Bits that hold ``coverage`` of the elements: the smallest b with sum(bits[:b+1]) >=
+        ceil(coverage * count), plus a sign bit when min < 0."""
+        import math
+        need = math.ceil(coverage * self.count)
+        cum, b = 0, 0
+        for b in range(STATS_BITS):
+            cum += int(self.bits[b])
+            if cum >= need:
+                break
+        return b + (1 if self.count and self.min < 0 else 0)
+
+    def percentile_abs(self, q: float) -> int:
+        """``np.partition(np.abs(x), k)[k]`` with k = int(count * q), from the value histogram:
+        what find_scale_by_percentile takes of a 1-byte record.  As there, the magnitude is taken
+        in the record's own dtype, where |-128| of an int8 record is -128."""
+        if self.values is None:
+            raise ValueError(f"percentile_abs needs the value histogram of a 1-byte record, {self.name or 'this'} "
+                             f"is {self.dtype}")
+        k = int(self.count * q)
+        if not 0 <= k < self.count:
+            raise ValueError(f"percentile_abs: q = {q} selects element {k} of {self.count}")
+        v = [int(c) for c in self.values]
+        if self.dtype == "int8":
+            order = [(-128, v[0])] + [(a, (v[128 + a] + v[128 - a]) if a else v[128]) for a in range(128)]
+        else:
+            order = list(enumerate(v))
+        cum = 0
+        for a, c in order:
+            cum += c
+            if cum > k:
+                return a
+        raise ValueError("percentile_abs: the value histogram does not add up to count")
+
+    def merge(self, other: "RecordStats") -> "RecordStats":
+        """Statistics of both together (the arithmetic of the kernel's flush)."""
+        if other.dtype != self.dtype:
+            raise ValueError(f"merge: {self.name} is {self.dtype}, {other.name} is {other.dtype}")
+        return RecordStats(self.name, self.dtype, self.count + other.count, min(self.min, other.min),
+                           max(self.max, other.max), _wrap_i64(self.sum + other.sum), self.bits + other.bits,
+                           None if self.values is None else self.values + other.values)
+
+    def equals(self, other: "RecordStats") -> bool:
+        """Every field but the name."""
+        return (self.dtype == other.dtype and (self.count, self.min, self.max, self.sum) ==
+                (other.count, other.min, other.max, other.sum) and np.array_equal(self.bits, other.bits) and
+                (self.values is None) == (other.values is None) and
+                (self.values is None or np.array_equal(self.values, other.values)))
+
+    def to_json(self) -> Dict[str, Any]:
+        """Python ints throughout: they survive beyond 2^53."""
+        return {"name": self.name, "dtype": self.dtype, "count": int(self.count), "min": int(self.min),
+                "max": int(self.max), "sum": int(self.sum), "bits": [int(b) for b in self.bits],
+                "values": None if self.values is None else [int(v) for v in self.values]}
+
+    @staticmethod
+    def from_json(d: Dict[str, Any]) -> "RecordStats":
+        return RecordStats(d["name"], d["dtype"], int(d["count"]), int(d["min"]), int(d["max"]), int(d["sum"]),
+                           np.array(d["bits"], np.uint64),
+                           None if d["values"] is None else np.array(d["values"], np.uint64))
+
+
+def record_stats(array, name: str = "") -> RecordStats:
+    """The statistics of one host array (int32, int8 or uint8), in numpy."""
+    x = np.asarray(array)
+    out = RecordStats.empty(str(x.dtype), name)
+    x = x.reshape(-1)
+    if x.size == 0:
+        return out
+    wide = x.astype(np.int64)
+    out.count = int(x.size)
+    out.min, out.max = int(wide.min()), int(wide.max())
+    out.sum = int(np.sum(wide, dtype=np.int64))
+    length = np.searchsorted(2 ** np.arange(32, dtype=np.int64), np.abs(wide), side="right")
+    out.bits = np.bincount(length, minlength=STATS_BITS).astype(np.uint64)
+    if out.values is not None:
+        out.values = np.bincount(wide - int(np.iinfo(x.dtype).min), minlength=STATS_VALUES).astype(np.uint64)
+    return out
+
+
+def trace_stats(path_or_bytes) -> Dict[str, RecordStats]:
+    """The statistics of every int32 / int8 / uint8 record of a trace file of either version, in
+    trace order; records of other dtypes are skipped.  Needs no GPU."""
+    return {k: record_stats(v, k) for k, v in read_trace(path_or_bytes).records.items() if str(v.dtype) in STATS_KIND}
+
+
+def merge_stats_dicts(parts: Sequence[Dict[str, RecordStats]]) -> Dict[str, RecordStats]:
+    """Name by name merge of several results (chunks, files, ranks), in first-seen order."""
+    out: Dict[str, RecordStats] = {}
+    for part in parts:
+        for k, s in part.items():
+            out[k] = out[k].merge(s) if k in out else s
+    return out
+
+
+def stats_to_json(stats: Dict[str, RecordStats]) -> Dict[str, Any]:
+    return {k: s.to_json() for k, s in stats.items()}
+
+
+def stats_from_json(d: Dict[str, Any]) -> Dict[str, RecordStats]:
+    return {k: RecordStats.from_json(v) for k, v in d.items()}
+
+
 def main(argv=None) -> int:
     import argparse
     p = argparse.ArgumentParser(prog="python -m tachikoma_amd.trace_format",
@@ -656,7 +817,12 @@ def main(argv=None) -> int:
         q.add_argument("src")
         q.add_argument("dst")
     sub.add_parser("info", help="sizes and coding plan of a file").add_argument("src")
+    sub.add_parser("stats", help="per-record statistics of the files, merged, as one JSON object").add_argument(
+        "files", nargs="+")
     args = p.parse_args(argv)
+    if args.cmd == "stats":
+        print(json.dumps(stats_to_json(merge_stats_dicts([trace_stats(f) for f in args.files]))))
+        return 0
     if args.cmd == "info":
         version = _header(_open(args.src))[0]
         info = packed_info(args.src) if version == PACKED_VERSION else \

@@ -18,6 +18,12 @@ unpack_trace): same names, same manifest, same digests (the digest is of the rec
 file), about half the bytes.  ``"packed"`` in a journal entry says which kind the file is, and a
 resumed job re-traces the chunks whose flag differs from its own.
 
+With ``stats`` every chunk's records are also reduced on the device to per-record statistics
+(GraphModule.stats_accumulator), written beside the chunk file as ``<chunk file>.stats.json`` before
+the chunk is journalled, and :func:`merge_stats` merges the journalled chunks' statistics into
+``<stem>.rank<r>.stats.json``; the journal itself does not change.  ``--stats-only`` writes only that
+merged file: compute-only runs, no chunk files, no journal, not resumable.
+
 On the device the chunk files are produced by :class:`GraphModuleTracer`: two pinned trace
 images alternate, so chunk c's file is written by a host thread while chunk c+1 runs and
 its records are copied D2H (the bench's file sink, overlapped with the next batch).  With
@@ -216,11 +222,16 @@ class GraphModuleTracer:
 
     def __init__(self, build_module: Callable[[int], "object"], inputs: Callable[[int, int], "object"],
                  model: str = "graph", input_name: str = "data", rank: int = 0, world: int = 1,
-                 packed: bool = False):
+                 packed: bool = False, stats: bool = False):
         self.build_module = build_module
         self.inputs = inputs
         self.model, self.input_name, self.rank, self.world = model, input_name, rank, world
         self.packed = bool(packed)
+        # with ``stats`` every chunk's per-record statistics are reduced on the device right after
+        # its run and written beside the chunk file as <chunk file>.stats.json (stats_file)
+        self.record_stats = bool(stats)
+        self.accumulators: Dict[int, "object"] = {}  # n_samples -> the module's StatsAccumulator
+        self.stats_slots: Dict[int, "object"] = {}  # per trace image: pinned host copy of its statistics
         self.stats: List[dict] = []  # packed: per chunk {"pack_ms", "copy_ms", "write_ms", "bytes"}
         self.modules: Dict[int, list] = {}  # n_samples -> [GraphModule, [TraceCapture x2], next slot]
         self.writer = concurrent.futures.ThreadPoolExecutor(max_workers=1)
@@ -270,6 +281,18 @@ class GraphModuleTracer:
         if slot_t is None:
             slot_t = self.digest_slots[id(cap)] = torch.empty(digest.shape, dtype=digest.dtype, pin_memory=True)
         slot_t.copy_(digest, non_blocking=True)
+        acc = stats_t = None
+        if self.record_stats:
+            # the statistics of exactly these records, on the run's stream before the next run can
+            # overwrite the buffers; like the digest they go into this image's own pinned slot,
+            # since the accumulator's entries are reset for the next chunk
+            acc = self.accumulator(n_samples)
+            acc.reset(stream)
+            acc.add(stream)
+            stats_t = self.stats_slots.get(id(cap))
+            if stats_t is None:
+                stats_t = self.stats_slots[id(cap)] = torch.empty(acc.words, dtype=torch.int64, pin_memory=True)
+            acc.copy_to(stats_t, stream)
         if self.packed:
             cap.pack(stream)  # waits for the run; the copy into the staging is on the packer's stream
         done = torch.cuda.Event()
@@ -281,11 +304,31 @@ class GraphModuleTracer:
             cap.write(path)
             if self.packed:
                 self.stats.append(dict(cap.stats, bytes=cap.size))
+            if acc is not None:
+                final = path[:-len(".partial")] if path.endswith(".partial") else path
+                write_stats_file(stats_file(final), acc.decode(stats_t))
             return int(slot_t.reshape(-1)[0].item()) & 0xFFFFFFFFFFFFFFFF
 
         fut = self.writer.submit(write)
         self.busy[id(cap)] = fut
         return fut
+
+    def accumulator(self, n_samples: int):
+        """The statistics accumulator of the module of ``n_samples`` (one per module)."""
+        if n_samples not in self.accumulators:
+            self.accumulators[n_samples] = self._module(n_samples, captures=False)[0].stats_accumulator()
+        return self.accumulators[n_samples]
+
+    def stats_only(self, sample_offset: int, n_samples: int) -> None:
+        """One chunk, compute only, merged into its module's accumulator: nothing is copied or
+        waited for."""
+        import torch
+        m = self._module(n_samples, captures=False)[0]
+        acc = self.accumulator(n_samples)
+        m.set_input(self.input_name, self.inputs(sample_offset, n_samples))
+        stream = torch.cuda.current_stream(m.module.device)
+        m.module.run(stream)
+        acc.add(stream)
 
     def check(self, path: str, replay: bool = False):
         """Verify one chunk file, packed or not, on the device (GraphModule.verify_trace; with
@@ -314,6 +357,8 @@ class GraphModuleTracer:
                 caps.clear()
         self.modules.clear()
         self.digest_slots.clear()
+        self.accumulators.clear()
+        self.stats_slots.clear()
 
 
 def check(tracer: GraphModuleTracer, out_dir: str, rank: int = 0, stem: str = "trace",
@@ -349,6 +394,69 @@ def check(tracer: GraphModuleTracer, out_dir: str, rank: int = 0, stem: str = "t
     return out
 
 
+def stats_file(chunk_path: str) -> str:
+    """The statistics sidecar of a chunk file."""
+    return chunk_path + ".stats.json"
+
+
+def rank_stats_file(out_dir: str, rank: int, stem: str = "trace") -> str:
+    return os.path.join(out_dir, f"{stem}.rank{rank}.stats.json")
+
+
+def write_stats_file(path: str, stats: Dict[str, "tf.RecordStats"]) -> None:
+    """{name: RecordStats.to_json()} as one JSON object, written under a temporary name and renamed:
+    a reader sees the whole file or none."""
+    tmp = path + ".tmp"
+    with open(tmp, "w") as f:
+        json.dump(tf.stats_to_json(stats), f, separators=(",", ":"))
+        f.flush()
+        os.fsync(f.fileno())
+    os.replace(tmp, path)
+
+
+def read_stats_file(path: str) -> Dict[str, "tf.RecordStats"]:
+    with open(path) as f:
+        return tf.stats_from_json(json.load(f))
+
+
+def merge_stats(out_dir: str, rank: int = 0, stem: str = "trace",
+                log: Optional[Callable[[str], None]] = None) -> Dict[str, "tf.RecordStats"]:
+    """Merge the statistics of every journalled chunk of this rank, in chunk order, into
+    ``<stem>.rank<r>.stats.json`` and return them.  A chunk's statistics come from its sidecar
+    (stats_file); where that is missing or does not parse they are recomputed on the host from the
+    chunk file itself (trace_format.trace_stats), which the log says."""
+    parts = []
+    for index, e in sorted(Journal(journal_file(out_dir, rank, stem)).entries().items()):
+        path = os.path.join(out_dir, str(e.get("file")))
+        try:
+            parts.append(read_stats_file(stats_file(path)))
+        except (OSError, ValueError, KeyError, TypeError):
+            if log:
+                log(f"rank {rank}: chunk {index} has no statistics file, reducing {os.path.basename(path)} on the host")
+            parts.append(tf.trace_stats(path))
+    merged = tf.merge_stats_dicts(parts)
+    write_stats_file(rank_stats_file(out_dir, rank, stem), merged)
+    return merged
+
+
+def run_stats_only(tracer: GraphModuleTracer, global_samples: int, chunk: int, out_dir: str, rank: int = 0,
+                   world: int = 1, stem: str = "trace",
+                   log: Optional[Callable[[str], None]] = None) -> Dict[str, "tf.RecordStats"]:
+    """The statistics of this rank's samples without a trace: every chunk runs compute-only and is
+    merged on the device (one statistics launch per chunk, no record leaves the device); at the end
+    the accumulators are read and ``<stem>.rank<r>.stats.json`` is written.  No chunk file and no
+    journal: the job is not resumable."""
+    os.makedirs(out_dir, exist_ok=True)
+    chunks = plan_chunks(global_samples, world, rank, chunk, out_dir, stem)
+    if log:
+        log(f"rank {rank}: {len(chunks)} chunks, statistics only")
+    for c in chunks:
+        tracer.stats_only(c.sample_offset, c.n_samples)
+    merged = tf.merge_stats_dicts([tracer.accumulators[n].result() for n in sorted(tracer.accumulators, reverse=True)])
+    write_stats_file(rank_stats_file(out_dir, rank, stem), merged)
+    return merged
+
+
 def main(argv=None) -> int:
     p = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     p.add_argument("--model", default="resnet50")
@@ -365,9 +473,18 @@ def main(argv=None) -> int:
     p.add_argument("--replay", action="store_true",
                    help="with --check: replay every chunk op by op from its recorded inputs instead, so that a "
                         "fault stays in its node; the JSON line also lists the faulty nodes")
+    p.add_argument("--stats", action="store_true",
+                   help="reduce every chunk's records to per-record statistics on the device and write them beside "
+                        "the chunk file (<chunk file>.stats.json); at the end merge them into "
+                        "<stem>.rank<r>.stats.json")
+    p.add_argument("--stats-only", action="store_true",
+                   help="write no chunk files and no journal: run the chunks compute-only, accumulate the statistics "
+                        "on the device and write <stem>.rank<r>.stats.json at the end; not resumable")
     args = p.parse_args(argv)
     if args.replay and not args.check:
         p.error("--replay goes with --check")
+    if args.stats_only and (args.check or args.stats or args.packed or args.verify):
+        p.error("--stats-only writes no trace: it does not go with --check, --stats, --packed or --verify")
     import torch
     from . import relay, zoo
     from .contrib import graph_executor
@@ -386,8 +503,18 @@ def main(argv=None) -> int:
         return graph_executor.GraphModule(lib["default"](device.index))
 
     tracer = GraphModuleTracer(build_module, proto.sample_inputs, model=proto.name, input_name=proto.input_name,
-                               rank=rank, world=world, packed=args.packed)
+                               rank=rank, world=world, packed=args.packed, stats=args.stats)
     log = lambda s: print(f"[trace_job] {s}", file=sys.stderr, flush=True)  # noqa: E731
+    if args.stats_only:
+        try:
+            run_stats_only(tracer, args.samples, args.chunk, args.out_dir, rank, world, log=log)
+        finally:
+            tracer.close()
+            if world > 1:
+                import torch.distributed as dist
+                dist.destroy_process_group()
+        log(f"statistics {rank_stats_file(args.out_dir, rank)}")
+        return 0
     if args.check:
         try:
             rows = check(tracer, args.out_dir, rank, log=log, replay=args.replay)
@@ -404,6 +531,9 @@ def main(argv=None) -> int:
                       verify=args.verify, log=log, packed=args.packed)
     finally:
         tracer.close()
+    if args.stats:
+        merge_stats(args.out_dir, rank, log=log)
+        log(f"statistics {rank_stats_file(args.out_dir, rank)}")
     if world > 1:
         import torch.distributed as dist
         allents: List = [None] * world
