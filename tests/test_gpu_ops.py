@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from oracle import qnn_ref as ref
+from tests.block_value_cases import blocked_shadow
 from tests.golden_util import load_array, load_cases, scale_const
 
 pytestmark = pytest.mark.gpu
@@ -61,17 +62,6 @@ def test_add_kat(tk, case):
                      a["lhs_zero_point"], a["rhs_scale"], a["rhs_zero_point"], a["output_scale"],
                      a["output_zero_point"])
     np.testing.assert_array_equal(out, load_array(case["expected"]))
-
-
-def blocked_shadow(x: np.ndarray) -> np.ndarray:
-    """Expected tk_conv2d_make_shadow layout of an NCHW 8-bit tensor: [C_pad16/16][N*H*W][16] uint8,
-    padded channels 0, uint8 stored xor 0x80."""
-    n, c, h, w = x.shape
-    cpad = (c + 15) // 16 * 16
-    b = x.view(np.uint8) ^ (0x80 if x.dtype == np.uint8 else 0)
-    full = np.zeros((n, cpad, h, w), np.uint8)
-    full[:, :c] = b
-    return full.reshape(n, cpad // 16, 16, h * w).transpose(1, 0, 3, 2).reshape(cpad // 16, n * h * w, 16)
 
 
 def _rand(rng, shape, dtype):

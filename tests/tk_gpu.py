@@ -235,7 +235,20 @@ def global_avg_pool(x):
     return out.cpu().numpy()
 
 
-def _rq_attrs(r, keep, input_scale, output_scale, output_zero_point, rounding="UPWARD", axis=1):
+def _poison(outs):
+    for t in outs:
+        t.fill_(0x5A5A5A5A if t.element_size() == 4 else 0x5A)
+
+
+def _rq_attrs(r, keep, input_scale, output_scale, output_zero_point, rounding="UPWARD", axis=1, rq_zp=0):
+    """rq_zp: the requantize input zero point, a scalar (input_zero_point) or a per-axis vector
+    (input_zero_points)."""
+    zpi = np.asarray(rq_zp)
+    if zpi.ndim == 0:
+        r.input_zero_point = int(zpi)
+    else:
+        keep.append(dev(zpi.astype(np.int32)))
+        r.input_zero_points = keep[-1].data_ptr()
     mode, ms, ss = requantize_plan(input_scale, output_scale, rounding)
     r.mode = mode
     r.axis = axis
@@ -251,11 +264,15 @@ def _rq_attrs(r, keep, input_scale, output_scale, output_zero_point, rounding="U
 
 def conv2d_block(x, w, bias, za, zw, s_in, s_out, zp_out, clip=None, strides=(1, 1), padding=(0, 0, 0, 0),
                  dilation=(1, 1), groups=1, out_dtype="int8", want_shadow=False, residual=None, add_params=None,
-                 block_is_rhs=False, rounding="UPWARD", algo=0, algos_only=False, zw_vec=None):
+                 block_is_rhs=False, rounding="UPWARD", algo=0, algos_only=False, zw_vec=None, rq_zp=0,
+                 algo_info=False, poison=False):
     """Fused conv -> bias_add -> requantize(axis 1) [-> qnn.add(., residual)] [-> clip] through
     tk_qnn_conv2d_block.  add_params = (ls, lz, rs, rz, os, oz) of the qnn.add (lhs = the block's
-    requantize output unless block_is_rhs).  algo: tk_block_attrs.algo; algos_only: return the
-    block's kernel list (tk_conv2d_block_algos) instead of running it."""
+    requantize output unless block_is_rhs).  rq_zp: the requantize input zero point, a scalar or a
+    per-channel vector.  algo: tk_block_attrs.algo; algos_only: return the block's kernel list
+    (tk_conv2d_block_algos) instead of running it, with algo_info as (algo, description) pairs
+    (tk_conv2d_block_algo_info).  poison: fill every record with 0x5A bytes first, so that an element
+    the kernel leaves out cannot hold an earlier run's value (the allocator hands blocks out again)."""
     lib = _lib.load()
     n, c, h, wd = x.shape
     o = w.shape[0]
@@ -269,6 +286,8 @@ def conv2d_block(x, w, bias, za, zw, s_in, s_out, zp_out, clip=None, strides=(1,
         outs.append(empty((n, o, oh, ow), out_dtype))
     if clip is not None:
         outs.append(empty((n, o, oh, ow), out_dtype))
+    if poison:
+        _poison(outs)
     a = _lib.tk_block_attrs()
     a.conv.strides[:] = list(strides)
     a.conv.padding[:] = list(padding)
@@ -280,7 +299,7 @@ def conv2d_block(x, w, bias, za, zw, s_in, s_out, zp_out, clip=None, strides=(1,
     if zw_vec is not None:  # per-output-channel kernel zero points
         keep.append(dev(np.asarray(zw_vec, np.int32)))
         a.conv.kernel_zero_points = keep[-1].data_ptr()
-    _rq_attrs(a.requantize, keep, s_in, s_out, zp_out, rounding=rounding)
+    _rq_attrs(a.requantize, keep, s_in, s_out, zp_out, rounding=rounding, rq_zp=rq_zp)
     if clip is not None:
         a.has_clip = 1
         a.clip_min, a.clip_max = clip
@@ -299,7 +318,16 @@ def conv2d_block(x, w, bias, za, zw, s_in, s_out, zp_out, clip=None, strides=(1,
         cnt = lib.tk_conv2d_block_algos(rx.ptr, rw.ptr, ctypes.byref(a), buf, 256)
         _lib.check(min(cnt, 0), "tk_conv2d_block_algos")
         assert cnt <= 256
-        return [int(buf[i]) for i in range(cnt)]
+        algos = [int(buf[i]) for i in range(cnt)]
+        if not algo_info:
+            return algos
+        descs = []
+        for al in algos:
+            text = ctypes.create_string_buffer(256)
+            _lib.check(lib.tk_conv2d_block_algo_info(rx.ptr, rw.ptr, ctypes.byref(a), al, text, 256),
+                       "tk_conv2d_block_algo_info")
+            descs.append(text.value.decode())
+        return list(zip(algos, descs))
     ws_bytes = lib.tk_qnn_conv2d_workspace_bytes(rx.ptr, rw.ptr, ctypes.byref(a.conv))
     shadow = packed = sums = patch = shadow_out = None
     st = stream()
@@ -327,3 +355,32 @@ def conv2d_block(x, w, bias, za, zw, s_in, s_out, zp_out, clip=None, strides=(1,
     if want_shadow:
         res.append(shadow_out.cpu().numpy())
     return res
+
+
+def dense_block(x, w, bias, za, zw, s_in, s_out, zp_out, clip=None, rq_zp=0, rounding="UPWARD", out_dtype="int8"):
+    """Fused dense -> bias_add -> requantize(axis 1) [-> clip] through tk_qnn_dense_block; returns the
+    records in chain order.  The records are filled with 0x5A bytes before the call."""
+    lib = _lib.load()
+    m, u = x.shape[0], w.shape[0]
+    xd, wdv, bd = dev(x), dev(w), dev(bias)
+    outs = [empty((m, u), "int32"), empty((m, u), "int32"), empty((m, u), out_dtype)]
+    if clip is not None:
+        outs.append(empty((m, u), out_dtype))
+    _poison(outs)
+    a = _lib.tk_block_attrs()
+    a.dense.input_zero_point = int(za)
+    a.dense.kernel_zero_point = int(zw)
+    keep = []
+    _rq_attrs(a.requantize, keep, s_in, s_out, zp_out, rounding=rounding, rq_zp=rq_zp)
+    if clip is not None:
+        a.has_clip = 1
+        a.clip_min, a.clip_max = clip
+    rx, rw, rb = ref(xd), ref(wdv), ref(bd)
+    ws_bytes = lib.tk_qnn_dense_workspace_bytes(rx.ptr, rw.ptr)
+    assert ws_bytes >= 0
+    ws = empty((max(ws_bytes, 16),), "uint8")
+    refs = [ref(t) for t in outs]
+    arr = (ctypes.POINTER(_lib.tk_tensor) * len(refs))(*[r.ptr for r in refs])
+    _sync_check(lib.tk_qnn_dense_block(rx.ptr, rw.ptr, rb.ptr, arr, len(refs), ctypes.byref(a),
+                                       ctypes.c_void_p(ws.data_ptr()), stream()), "tk_qnn_dense_block")
+    return [t.cpu().numpy() for t in outs]
