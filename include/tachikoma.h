@@ -680,7 +680,15 @@ int tk_module_copy_trace(tk_module* mod, double* out, int max_chunks);
  * declares as the clip of the record directly before them in the image (same dtype and shape: the
  * clip output of a conv, dense or add block, or a TK_NODE_CLIP of the preceding record): those are
  * coded as clamps of that record (format below; TK_WIRE_CLAMP=0 in the environment at
- * tk_module_create keeps them raw).  After each chunk's graph an encode kernel on
+ * tk_module_create keeps them raw).  An int32 record coded as the difference from the record before
+ * it, which its node declares as the bias_add of that record (output 1 of a conv or dense block,
+ * or a TK_NODE_BIAS_ADD of the preceding record) with a compact int32 bias of the axis' length,
+ * is coded less that bias per channel (the addend of the format below), so that its blocks are
+ * constant also where they straddle channel planes.  The bias values are copied once when the
+ * packed plan is built, into a device buffer the encoder reads and a host copy of that buffer the
+ * decoder reads; neither reads the node's live bias, so parameters loaded later make the
+ * prediction worse, never the image wrong.  TK_WIRE_BIAS=0 in the environment at tk_module_create
+ * keeps plain differences.  After each chunk's graph an encode kernel on
  * a module-owned wire stream reads them from their own device buffers and writes the wire format
  * below straight into a pinned host slot (a ring of three worst-case-sized chunk slots); the
  * other records still go through the mirror, copied in runs of adjacent records on the wire
@@ -701,7 +709,7 @@ int tk_module_wire_stats(tk_module* mod, double* out, int max_chunks);
  * coded as an int32 base (the block minimum) plus offsets of 0..4 bytes each, in byte planes;
  * a record with diff != 0 is coded as its wrap-around difference from the record before it, which
  * must have the same element count.  `offset` is the record's byte offset in the trace image
- * (any alignment).  `kind` is the element kind: 0 int32 (the above), 1 int8, 2 uint8.  A 1-byte
+ * (any alignment).  `kind` is the element kind: 0 int32 (the above), 1 int8, 2 uint8 (3: below).  A 1-byte
  * record keeps the geometry (256-element blocks, 64-block segments, base[nb] / width[nb] header)
  * with `offset` / `n_elems` counting bytes and two block forms: width 0 is a constant block (the
  * value in byte 0 of the base), width 1 one raw plane of the record's own bytes.  With diff != 0 a
@@ -710,7 +718,22 @@ int tk_module_wire_stats(tk_module* mod, double* out, int max_chunks);
  * maximum in the record's dtype, stored in base bytes 0 / 1, and width 1 is still the raw plane
  * (the escape of a block the clamp does not reproduce), so any data round-trips; the decoder reads
  * the predecessor from image bytes already present and refuses other widths.  One buffer may mix
- * kinds.  tk_wire_bound: the worst-case wire size.  tk_wire_encode_host: the reference
+ * kinds.  Bias coding (a bias_add record after its convolution): a record of kind 3 is an int32
+ * record with diff != 0 that also carries a per-channel addend, given beside the records as
+ * addends[i] (a tk_wire_addend per record, read for records of kind 3 only): the coded value of
+ * element e is then rec[e] - prev[e] - addend[(e / plane) % channels] with int32 wrap-around,
+ * `plane` being the product of the dims after the bias axis and `channels` the dim on it (plane = 1
+ * for a dense record).  It follows, and is followed by, records of kind 0 and 3 alike.  The addend
+ * is a predictor, not a fact: any values round-trip any data, and a block the prediction does not
+ * flatten takes the width its range needs.  `addend` (channels int32 values) is read by whoever
+ * reads the sources: a host pointer for tk_wire_encode_host_bias and tk_wire_decode_bias, a device
+ * pointer for tk_wire_encode_device_bias (the entry points of the same names with `addends`);
+ * encoder and decoder must be given the same values.  A record of kind 3 without diff, of 2^31
+ * elements or more, or whose addends[i] has a null addend or a plane or channels below 1, is
+ * refused (TK_ERR_INVALID_ARG).  Every entry point that takes no addends -- tk_wire_encode_host,
+ * tk_wire_decode, tk_wire_encode_device and, with them, the packed trace files' tk_wire_check,
+ * tk_wire_pack_device and tk_wire_unpack_device (format version 2) -- refuses a record of kind 3
+ * with TK_ERR_UNSUPPORTED.  tk_wire_bound: the worst-case wire size.  tk_wire_encode_host: the reference
  * encoder (reads the records from `image`), returns the wire bytes written.  tk_wire_decode:
  * widens `wire` into `image` on up to `threads` pool threads (<= 0: the pool, which is sized from
  * the CPU affinity mask, at most 16, TK_WIRE_THREADS overrides; tk_wire_threads reports it); a
@@ -737,6 +760,10 @@ typedef struct {
   int32_t diff;
   int32_t kind;
 } tk_wire_record;
+typedef struct {
+  int32_t plane, channels;
+  const int32_t* addend;
+} tk_wire_addend;
 int64_t tk_wire_bound(const tk_wire_record* recs, int n_recs);
 int64_t tk_wire_encode_host(const tk_wire_record* recs, int n_recs, const void* image, int64_t image_bytes,
                             void* wire, int64_t wire_cap);
@@ -748,6 +775,12 @@ int64_t tk_wire_pack_device(const tk_wire_record* recs, int n_recs, const void* 
                             int64_t wire_cap, void* stream);
 int tk_wire_pack_tile(void);
 int tk_wire_threads(void);
+int64_t tk_wire_encode_host_bias(const tk_wire_record* recs, const tk_wire_addend* addends, int n_recs, const void* image,
+                                 int64_t image_bytes, void* wire, int64_t wire_cap);
+int tk_wire_decode_bias(const tk_wire_record* recs, const tk_wire_addend* addends, int n_recs, const void* wire,
+                        int64_t wire_bytes, void* image, int64_t image_bytes, int threads);
+int tk_wire_encode_device_bias(const tk_wire_record* recs, const tk_wire_addend* addends, int n_recs,
+                               const void* const* src, void* wire, int64_t wire_cap, void* stream);
 
 /* The way back in: checking a wire buffer on the host, decoding it on the device.
  *

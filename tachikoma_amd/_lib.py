@@ -312,7 +312,15 @@ class tk_wire_record(ctypes.Structure):
         ("offset", ctypes.c_int64),
         ("n_elems", ctypes.c_int64),
         ("diff", ctypes.c_int32),
-        ("kind", ctypes.c_int32),      # 0 int32, 1 int8, 2 uint8
+        ("kind", ctypes.c_int32),      # 0 int32, 1 int8, 2 uint8, 3 int32 bias-coded (tk_wire_addend)
+    ]
+
+
+class tk_wire_addend(ctypes.Structure):
+    _fields_ = [
+        ("plane", ctypes.c_int32),
+        ("channels", ctypes.c_int32),
+        ("addend", ctypes.c_void_p),   # const int32_t*: host or device, as the sources are
     ]
 
 
@@ -455,6 +463,12 @@ SIGNATURES = {
     "tk_wire_decode": (ctypes.c_int, [ctypes.POINTER(tk_wire_record), ctypes.c_int, _VP, _I64, _VP, _I64, ctypes.c_int]),
     "tk_wire_encode_device": (ctypes.c_int, [ctypes.POINTER(tk_wire_record), ctypes.c_int, ctypes.POINTER(_VP), _VP,
                                              _I64, _VP]),
+    "tk_wire_encode_host_bias": (_I64, [ctypes.POINTER(tk_wire_record), ctypes.POINTER(tk_wire_addend), ctypes.c_int, _VP,
+                                        _I64, _VP, _I64]),
+    "tk_wire_decode_bias": (ctypes.c_int, [ctypes.POINTER(tk_wire_record), ctypes.POINTER(tk_wire_addend), ctypes.c_int,
+                                           _VP, _I64, _VP, _I64, ctypes.c_int]),
+    "tk_wire_encode_device_bias": (ctypes.c_int, [ctypes.POINTER(tk_wire_record), ctypes.POINTER(tk_wire_addend),
+                                                  ctypes.c_int, ctypes.POINTER(_VP), _VP, _I64, _VP]),
     "tk_wire_pack_device": (_I64, [ctypes.POINTER(tk_wire_record), ctypes.c_int, ctypes.POINTER(_VP), _VP, _I64, _VP]),
     "tk_wire_pack_tile": (ctypes.c_int, []),
     "tk_wire_threads": (ctypes.c_int, []),

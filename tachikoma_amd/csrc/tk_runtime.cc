@@ -298,6 +298,12 @@ struct PackPlan {
   };
   std::vector<WireChunk> wchunks;
   void* wire_segs = nullptr;   // device WireSegDev entries of every chunk
+  // Bias coding: the bias vectors of the records coded with an addend, copied once when the plan
+  // is built.  The encoder subtracts the device copy and the decoder adds the host copy, which is
+  // a copy of that device copy; neither reads a node's live bias, so new parameters can make the
+  // prediction worse but never the two sides disagree.
+  int32_t* addend_dev = nullptr;
+  std::vector<int32_t> addend_host;
   std::vector<void*> slots;    // pinned ring of worst-case-sized chunk slots
   uint32_t* cursors = nullptr; // device, one per slot
   std::vector<hipEvent_t> slot_done;  // decode of the slot's last use (decode stream)
@@ -309,6 +315,7 @@ struct PackPlan {
     for (auto e : slot_done) (void)hipEventDestroy(e);
     for (void* p : slots) (void)hipHostFree(p);
     if (wire_segs) (void)hipFree(wire_segs);
+    if (addend_dev) (void)hipFree(addend_dev);
     if (cursors) (void)hipFree(cursors);
     for (int m = 0; m < 2; ++m) {
       for (auto x : ge[m]) (void)hipGraphExecDestroy(x);
@@ -367,7 +374,8 @@ struct tk_module {
   // trace wire of the packed capture: on unless TK_TRACE_WIRE=0 was set when the module was
   // created; wire traffic and decodes run on two streams of the module's own
   // TK_WIRE_CLAMP=0 at creation keeps the clip records raw (the same library's comparison run)
-  bool trace_wire = true, wire_forced_off = false, wire_clamp = true;
+  // TK_WIRE_BIAS=0 at creation keeps the bias_add records plain differences (likewise)
+  bool trace_wire = true, wire_forced_off = false, wire_clamp = true, wire_bias = true;
   hipStream_t wire_s = nullptr, dec_s = nullptr;
   hipEvent_t wire_tail = nullptr, decode_tail = nullptr;  // last wire work / decode of the last wire run
   bool wire_tail_used = false;
@@ -545,6 +553,7 @@ int tk_module_create(const tk_node* nodes, int n_nodes, tk_module** out) {
   auto mod = std::make_unique<tk_module>();
   if (const char* e = std::getenv("TK_TRACE_WIRE")) mod->wire_forced_off = e[0] == '0' && e[1] == 0;
   if (const char* e = std::getenv("TK_WIRE_CLAMP")) mod->wire_clamp = !(e[0] == '0' && e[1] == 0);
+  if (const char* e = std::getenv("TK_WIRE_BIAS")) mod->wire_bias = !(e[0] == '0' && e[1] == 0);
   mod->nodes.resize(n_nodes);
   for (int i = 0; i < n_nodes; ++i) {
     const tk_node& src = nodes[i];
@@ -740,6 +749,11 @@ struct PackRecord {
   const tk_tensor* t;
   bool wire, diff;  // coded on the wire; as the difference from the record before it
   bool clamp;       // coded on the wire as a clamp of the record before it (1-byte)
+  // a differenced record that is the bias_add of the record before it: the bias vector, the
+  // geometry of its axis and where its snapshot lies in the plan's addend buffers (int32 elements)
+  const tk_tensor* bias = nullptr;
+  int32_t plane = 0, channels = 0;
+  int64_t addend_at = 0;
 };
 
 // the records in host order; overlapping destinations are refused
@@ -770,8 +784,28 @@ static const void* clip_input(const tk::Node& n, int k) {
   return d.kind == TK_NODE_CLIP && k == 0 ? tk::ptr(&n.in[0].t) : nullptr;
 }
 
+// The bias that output k of node n adds to the tensor at `from`, where the node declares that
+// output as the bias_add of that tensor: output 1 of a conv or dense block over its output 0, or a
+// TK_NODE_BIAS_ADD over its input.  *axis: the record's axis the bias runs along.
+static const tk_tensor* bias_input(const tk::Node& n, int k, const void* from, int* axis) {
+  const tk_node& d = n.desc;
+  if ((d.kind == TK_NODE_CONV_BLOCK || d.kind == TK_NODE_DENSE_BLOCK) && k == 1 && d.n_inputs >= 3 &&
+      tk::ptr(&n.out[0].t) == from) {
+    *axis = d.kind == TK_NODE_CONV_BLOCK ? 1 : n.out[1].t.ndim - 1;
+    return &n.in[2].t;
+  }
+  if (d.kind == TK_NODE_BIAS_ADD && k == 0 && d.n_inputs >= 2 && tk::ptr(&n.in[0].t) == from) {
+    *axis = d.attrs.bias_add.axis < 0 ? d.attrs.bias_add.axis + n.out[0].t.ndim : d.attrs.bias_add.axis;
+    return &n.in[1].t;
+  }
+  return nullptr;
+}
+
 // int32 records are coded; one that follows (in the image) a coded record of its own shape is
-// coded as the difference from it (every bias_add after its convolution).  A compact 1-byte
+// coded as the difference from it (every bias_add after its convolution), and where its node
+// declares it as the bias_add of that record, with a compact int32 bias of the axis' length and
+// fewer than 2^31 elements, as the difference less the bias (tk_wire.h: bias coding; the values are
+// a snapshot the plan takes, never the live tensor; TK_WIRE_BIAS=0 keeps plain differences).  A compact 1-byte
 // record that its node declares as the clip of the record before it in the image (same dtype
 // and shape) is coded as a clamp of that record; every other 1-byte record stays raw.  Returns
 // whether any record is coded.
@@ -792,6 +826,15 @@ static bool decide_coding(const tk_module* mod, std::vector<PackRecord>& recs) {
     any |= c.wire;
     if (!c.wire || r == 0 || !recs[r - 1].wire) continue;
     c.diff = same_shape && tk::is_int(b, 32) && c.src != recs[r - 1].src;
+    int axis = 0;
+    const tk_tensor* bias = c.diff && mod->wire_bias ? bias_input(mod->nodes[c.node], c.out, recs[r - 1].src, &axis) : nullptr;
+    if (!bias || !bias->data || axis < 0 || axis >= a->ndim || !tk::is_int(bias, 32) || !tk::compact(bias) ||
+        tk::numel(bias) != a->shape[axis] || a->shape[axis] < 1 || a->shape[axis] >= ((int64_t)1 << 31) ||
+        tk::numel(a) >= ((int64_t)1 << 31))
+      continue;
+    int64_t plane = 1;
+    for (int d = axis + 1; d < a->ndim; ++d) plane *= a->shape[d];
+    c.bias = bias, c.plane = (int32_t)plane, c.channels = (int32_t)a->shape[axis];
   }
   return any;
 }
@@ -799,7 +842,7 @@ static bool decide_coding(const tk_module* mod, std::vector<PackRecord>& recs) {
 // A chunk's wire tables, planned by tk::wire_plan from its coded records (`coded`: their indices in
 // `recs`): the encoder's segments (record buffers on the device), the host decoder's (image bytes),
 // the decode units and the size of a slot with every block raw.
-static int chunk_wire_tables(const std::vector<PackRecord>& recs, const std::vector<size_t>& coded,
+static int chunk_wire_tables(const std::vector<PackRecord>& recs, const std::vector<size_t>& coded, const PackPlan* plan,
                              PackPlan::WireChunk* wc, std::vector<tk::WireSegDev>& wire_segs) {
   std::vector<tk_wire_record> wrecs;  // offsets are not used here
   for (size_t q = 0; q < coded.size(); ++q) {
@@ -826,8 +869,29 @@ static int chunk_wire_tables(const std::vector<PackRecord>& recs, const std::vec
     const tk::WireSegAddr img = tk::wire_seg_addr(sr, kind, r.host, pv ? pv->host : nullptr);
     wire_segs.push_back({dev.at, dev.prev, sr.n, kind});
     wc->segs.push_back({img.at, img.prev, sr.n, kind});
+    if (r.bias) {  // each side is handed its own copy of the plan's snapshot
+      tk::wire_seg_bias(&wire_segs.back(), plan->addend_dev + r.addend_at, r.plane, r.channels, sr.e0);
+      tk::wire_seg_bias(&wc->segs.back(), plan->addend_host.data() + r.addend_at, r.plane, r.channels, sr.e0);
+    }
   }
   for (size_t q : coded) wc->coded_bytes += recs[q].bytes;
+  return TK_OK;
+}
+
+// The plan's snapshot of the bias vectors its records are coded with (PackPlan::addend_dev /
+// addend_host): each vector copied device to device into one buffer, and that buffer to the host.
+static int snapshot_addends(PackPlan* plan, std::vector<PackRecord>& recs) {
+  int64_t total = 0;
+  for (PackRecord& r : recs)
+    if (r.bias) r.addend_at = total, total += r.channels;
+  if (!total) return TK_OK;
+  TK_HIP(hipMalloc((void**)&plan->addend_dev, (size_t)total * sizeof(int32_t)));
+  for (const PackRecord& r : recs)
+    if (r.bias)
+      TK_HIP(hipMemcpy(plan->addend_dev + r.addend_at, tk::ptr(r.bias), (size_t)r.channels * sizeof(int32_t),
+                       hipMemcpyDeviceToDevice));
+  plan->addend_host.resize((size_t)total);
+  TK_HIP(hipMemcpy(plan->addend_host.data(), plan->addend_dev, (size_t)total * sizeof(int32_t), hipMemcpyDeviceToHost));
   return TK_OK;
 }
 
@@ -880,7 +944,7 @@ static int cut_chunks(const tk_module* mod, const std::vector<PackRecord>& recs,
     cut = upto;
     if (!plan->wire) continue;
     if (!w_rec.empty())
-      if (const int rc = chunk_wire_tables(recs, w_rec, &wc, wire_segs)) return rc;
+      if (const int rc = chunk_wire_tables(recs, w_rec, plan, &wc, wire_segs)) return rc;
     plan->wchunks.push_back(std::move(wc));
   }
   if (cut != plan->span || next_rec != recs.size()) {
@@ -1011,6 +1075,8 @@ static int build_pack_plan(tk_module* mod, const std::vector<void*>& dst, PackPl
   plan->span = recs.back().host + recs.back().bytes - plan->host_lo;
   std::vector<PackRecHost> table;
   std::vector<tk::WireSegDev> wire_segs;
+  if (plan->wire)
+    if (const int rc = snapshot_addends(plan.get(), recs)) return rc;
   if (const int rc = cut_chunks(mod, recs, plan.get(), table, wire_segs)) return rc;
   if (const int rc = alloc_pack_resources(mod, plan.get(), table, wire_segs)) return rc;
   if (const int rc = capture_chunk_graphs(mod, plan.get())) return rc;

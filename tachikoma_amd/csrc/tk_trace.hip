@@ -173,7 +173,32 @@ int pack_records_impl(const void* table, int nrec, int64_t blocks, void* mirror,
 // uint8 (int8 with the sign bit flipped); the butterfly gives the block's lo and hi, every lane
 // tests clamp(prev, lo, hi) == src on its 16 bytes and a 16-lane AND decides between width 0 and
 // the raw plane, which is the lane's 16 loaded bytes stored as they are.
+//
+// Bias coding (an int32 segment with an addend): after the predecessor, a lane subtracts from each
+// of its 16 values the addend of that element's channel.  The segment's first element lies at
+// position r0 of channel c0's plane (host-computed), so the lane's first one, e0 elements on, is
+// found with one 32-bit division; from there the walk steps position and channel per element and
+// reloads the addend only where the channel changes (a lane crosses several planes where plane < 16).
+// The channel is always one of the addend's, so the walk may run past the record's end.
 __device__ __forceinline__ uint32_t wire_byte(const uint32_t* w, int j) { return (w[j >> 2] >> (8 * (j & 3))) & 0xFFu; }
+
+__device__ __forceinline__ void wire_sub_addend(uint32_t* x, const WireSegDev& sg, int e0) {
+  const uint32_t plane = (uint32_t)sg.plane, channels = (uint32_t)sg.channels;
+  const uint32_t t = (uint32_t)sg.r0 + (uint32_t)e0;
+  const uint32_t q = t / plane;
+  uint32_t r = t - q * plane;
+  uint32_t c = ((uint32_t)sg.c0 + q) % channels;
+  uint32_t a = (uint32_t)sg.addend[c];
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    x[j] -= a;
+    if (++r == plane) {
+      r = 0;
+      c = c + 1 == channels ? 0 : c + 1;
+      a = (uint32_t)sg.addend[c];
+    }
+  }
+}
 
 // The packer of trace files (tk_wire_pack_device) runs the same code twice around a prefix sum, so
 // that segment i lies where the host encoder puts it whatever order the workgroups finish in:
@@ -270,6 +295,7 @@ __global__ __launch_bounds__(256) void wire_encode_kernel(const WireSegDev* __re
                 v[p][4 * q + 3] -= (uint32_t)a.w;
           }
         }
+        if (sg.addend) wire_sub_addend(v[p], sg, e0);
 #pragma unroll
         for (int j = 0; j < 16; ++j) mn = min(mn, (int32_t)v[p][j]), mx = max(mx, (int32_t)v[p][j]);
       } else {
@@ -279,10 +305,14 @@ __global__ __launch_bounds__(256) void wire_encode_kernel(const WireSegDev* __re
           if (e0 + j < n) {
             x = (uint32_t)src32[e0 + j];
             if (prev32) x -= (uint32_t)prev32[e0 + j];
-            mn = min(mn, (int32_t)x), mx = max(mx, (int32_t)x);
           }
           v[p][j] = x;
         }
+        // (the walk also passes over the elements past the record's end: they are never stored)
+        if (sg.addend && e0 < n) wire_sub_addend(v[p], sg, e0);
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+          if (e0 + j < n) mn = min(mn, (int32_t)v[p][j]), mx = max(mx, (int32_t)v[p][j]);
       }
 #pragma unroll
       for (int m = 8; m >= 1; m >>= 1) {
@@ -859,12 +889,16 @@ __global__ __launch_bounds__(kBlock) void digest_kernel(const uint8_t* __restric
 
 namespace {
 // the encoders' view of a plan's segments: record i is read from src[i]
-std::vector<tk::WireSegDev> source_segs(const tk::WirePlan& plan, const tk_wire_record* recs, const void* const* src) {
+std::vector<tk::WireSegDev> source_segs(const tk::WirePlan& plan, const tk_wire_record* recs, const void* const* src,
+                                        const tk_wire_addend* addends = nullptr) {
   std::vector<tk::WireSegDev> segs;
   segs.reserve(plan.segs.size());
   for (const tk::WireSegRef& r : plan.segs) {
-    const tk::WireSegAddr a = tk::wire_seg_addr(r, recs[r.rec].kind, src[r.rec], recs[r.rec].diff ? src[r.rec - 1] : nullptr);
-    segs.push_back({a.at, a.prev, r.n, recs[r.rec].kind});
+    const int kind = tk::wire_seg_kind(recs[r.rec].kind);
+    const tk::WireSegAddr a = tk::wire_seg_addr(r, kind, src[r.rec], recs[r.rec].diff ? src[r.rec - 1] : nullptr);
+    segs.push_back({a.at, a.prev, r.n, kind});
+    if (const tk_wire_addend* ad = tk::wire_addend_of(recs, addends, r.rec))
+      tk::wire_seg_bias(&segs.back(), ad->addend, ad->plane, ad->channels, r.e0);
   }
   return segs;
 }
@@ -912,13 +946,18 @@ int tk_digest_bytes(const void* data, int64_t nbytes, uint64_t* out_device, void
 
 int tk_wire_encode_device(const tk_wire_record* recs, int n_recs, const void* const* src, void* wire,
                           int64_t wire_cap, void* stream) {
+  return tk_wire_encode_device_bias(recs, nullptr, n_recs, src, wire, wire_cap, stream);
+}
+
+int tk_wire_encode_device_bias(const tk_wire_record* recs, const tk_wire_addend* addends, int n_recs,
+                               const void* const* src, void* wire, int64_t wire_cap, void* stream) {
   tk::WirePlan plan;
-  if (const int rc = tk::wire_plan(recs, n_recs, -1, "tk_wire_encode_device", &plan)) return rc;
+  if (const int rc = tk::wire_plan(recs, n_recs, -1, "tk_wire_encode_device", &plan, addends)) return rc;
   if (!src || !wire || wire_cap < plan.bound) {
     tk::set_error("tk_wire_encode_device: the wire buffer is smaller than tk_wire_bound");
     return TK_ERR_INVALID_ARG;
   }
-  const std::vector<tk::WireSegDev> segs = source_segs(plan, recs, src);
+  const std::vector<tk::WireSegDev> segs = source_segs(plan, recs, src, addends);
   hipStream_t s = tk::as_stream(stream);
   void* dev = nullptr;
   TK_HIP(hipMalloc(&dev, segs.size() * sizeof(tk::WireSegDev) + 64));

@@ -1,6 +1,7 @@
 // Host side of the trace wire format (tk_wire.h): the planner every encoder and decoder lays its
 // records out with, the decoder that widens a wire buffer into the trace image (and rebuilds
-// clamp-predicted 1-byte records from the image bytes before them) on a fixed thread pool, and a
+// clamp-predicted 1-byte records from the image bytes before them, and bias-coded int32 records
+// one channel run at a time) on a fixed thread pool, and a
 // reference encoder so the decoder is testable without a device.  Plain C++ (no HIP): also
 // compiled alone into the sanitizer check of tools/wire_check.cc.
 #include "tk_wire.h"
@@ -20,7 +21,8 @@
 namespace tk {
 void set_error(const std::string& msg);
 
-int wire_plan(const tk_wire_record* recs, int n_recs, int64_t image_bytes, const char* who, WirePlan* p) {
+int wire_plan(const tk_wire_record* recs, int n_recs, int64_t image_bytes, const char* who, WirePlan* p,
+              const tk_wire_addend* addends, bool bias_ok) {
   if (!recs || n_recs < 1) {
     set_error(std::string(who) + ": no records");
     return TK_ERR_INVALID_ARG;
@@ -28,12 +30,27 @@ int wire_plan(const tk_wire_record* recs, int n_recs, int64_t image_bytes, const
   int64_t n_seg = 0;
   for (int i = 0; i < n_recs; ++i) {
     const int kind = recs[i].kind;
+    if (kind == kWireI32Bias &&
+        (!recs[i].diff || recs[i].n_elems >= ((int64_t)1 << 31) ||
+         (addends && (!addends[i].addend || addends[i].plane < 1 || addends[i].channels < 1)))) {
+      set_error(std::string(who) + ": record " + std::to_string(i) +
+                " is bias-coded (kind 3) but is not a differenced record of fewer than 2^31 elements with an addend "
+                "and a plane and channels of at least 1");
+      return TK_ERR_INVALID_ARG;
+    }
+    if (kind == kWireI32Bias && !addends && !bias_ok) {
+      set_error(std::string(who) + ": record " + std::to_string(i) +
+                " is bias-coded (kind 3), which this entry point takes no addends for (packed trace files, format "
+                "version 2, and the device decoder do not code them)");
+      return TK_ERR_UNSUPPORTED;
+    }
     const int64_t esize = wire_elem_bytes(kind);
-    const bool inside = kind >= kWireI32 && kind <= kWireU8 && recs[i].offset >= 0 && recs[i].n_elems >= 1 &&
+    const bool inside = kind >= kWireI32 && kind <= kWireI32Bias && recs[i].offset >= 0 && recs[i].n_elems >= 1 &&
                         recs[i].n_elems <= ((int64_t)1 << 40) &&
                         (image_bytes < 0 ||
                          (recs[i].offset <= image_bytes && esize * recs[i].n_elems <= image_bytes - recs[i].offset));
-    if (!inside || (recs[i].diff && (i == 0 || recs[i - 1].n_elems != recs[i].n_elems || recs[i - 1].kind != kind))) {
+    if (!inside || (recs[i].diff && (i == 0 || recs[i - 1].n_elems != recs[i].n_elems ||
+                                     wire_seg_kind(recs[i - 1].kind) != wire_seg_kind(kind)))) {
       set_error(std::string(who) + ": record " + std::to_string(i) +
                 " is of no known kind, lies outside the image or follows (diff) a record of another size or kind");
       return TK_ERR_INVALID_ARG;
@@ -148,10 +165,12 @@ class Pool {
 // ---------------------------------------------------------------- decoder
 // image words are read and written through memcpy: NDArray-list payload offsets are 8-byte
 // aligned only by layout, and the decoder promises nothing about alignment at all
-template <int W, bool D>
-void widen(char* dst, const char* prev, const uint8_t* p, int cnt, uint32_t base) {
+// A: a bias-coded block that holds more than one channel run takes its constant per element from
+// `add` (base + the element's addend, laid out by the caller) instead of from `base`
+template <int W, bool D, bool A>
+void widen(char* dst, const char* prev, const uint8_t* p, int cnt, uint32_t base, const uint32_t* add) {
   for (int i = 0; i < cnt; ++i) {
-    uint32_t v = base;
+    uint32_t v = A ? add[i] : base;
     if (W >= 1) v += p[i];
     if (W >= 2) v += (uint32_t)p[cnt + i] << 8;
     if (W >= 3) v += (uint32_t)p[2 * cnt + i] << 16;
@@ -164,16 +183,30 @@ void widen(char* dst, const char* prev, const uint8_t* p, int cnt, uint32_t base
     std::memcpy(dst + 4 * (int64_t)i, &v, 4);
   }
 }
-template <bool D>
-void widen_w(int w, char* dst, const char* prev, const uint8_t* p, int cnt, uint32_t base) {
+template <bool D, bool A = false>
+void widen_w(int w, char* dst, const char* prev, const uint8_t* p, int cnt, uint32_t base, const uint32_t* add = nullptr) {
   switch (w) {
-    case 0: return widen<0, D>(dst, prev, p, cnt, base);
-    case 1: return widen<1, D>(dst, prev, p, cnt, base);
-    case 2: return widen<2, D>(dst, prev, p, cnt, base);
-    case 3: return widen<3, D>(dst, prev, p, cnt, base);
-    default: return widen<4, D>(dst, prev, p, cnt, base);
+    case 0: return widen<0, D, A>(dst, prev, p, cnt, base, add);
+    case 1: return widen<1, D, A>(dst, prev, p, cnt, base, add);
+    case 2: return widen<2, D, A>(dst, prev, p, cnt, base, add);
+    case 3: return widen<3, D, A>(dst, prev, p, cnt, base, add);
+    default: return widen<4, D, A>(dst, prev, p, cnt, base, add);
   }
 }
+
+// The channel runs of a bias-coded segment (tk_wire.h): a cursor over its elements that knows the
+// channel of the element it stands on and how many elements are left in that channel's plane.
+struct BiasWalk {
+  const int32_t* addend;
+  int32_t plane, channels, c, r;
+  template <typename Seg>
+  explicit BiasWalk(const Seg& s) : addend(s.addend), plane(s.plane), channels(s.channels), c(s.c0), r(s.r0) {}
+  int run(int left) const { return std::min(left, plane - r); }  // elements up to the plane's end
+  uint32_t value() const { return (uint32_t)addend[c]; }
+  void advance(int k) {  // k <= run()
+    if ((r += k) == plane) r = 0, c = c + 1 == channels ? 0 : c + 1;
+  }
+};
 
 // 1-byte blocks: dst = clamp(prev, lo, hi) in the record's dtype, 32 bytes at a time.  int8 is
 // compared as uint8 with the sign bit flipped (`flip` 0x80; lo and hi come flipped already), so
@@ -240,14 +273,40 @@ int64_t decode_seg(const WireJob& j, int64_t i, const char* payload, int64_t pay
     }
     return wire_align(len, 64);
   }
+  BiasWalk walk(sg);
   for (int b = 0; b < nb; ++b) {
     const int cnt = std::min(kWireBlock, sg.n - b * kWireBlock);
     const int w = widths[b];
     int32_t base;
     std::memcpy(&base, p + 4 * b, 4);
     char* dst = sg.dst + 4 * (int64_t)b * kWireBlock;
-    if (sg.prev) widen_w<true>(w, dst, sg.prev + 4 * (int64_t)b * kWireBlock, q, cnt, (uint32_t)base);
-    else widen_w<false>(w, dst, nullptr, q, cnt, (uint32_t)base);
+    const char* prev = sg.prev ? sg.prev + 4 * (int64_t)b * kWireBlock : nullptr;
+    if (sg.addend && prev) {
+      if (walk.run(cnt) == cnt) {  // one channel: the block's constant is its base plus that addend
+        widen_w<true>(w, dst, prev, q, cnt, (uint32_t)base + walk.value());
+        walk.advance(cnt);
+      } else if (w == 0) {  // the prediction held: each channel run is its predecessor plus a constant
+        for (int i = 0; i < cnt;) {
+          const int k = walk.run(cnt - i);
+          widen<0, true, false>(dst + 4 * i, prev + 4 * i, q, k, (uint32_t)base + walk.value(), nullptr);
+          walk.advance(k);
+          i += k;
+        }
+      } else {  // the constants of the block's channel runs, then one pass over the whole block
+        uint32_t add[kWireBlock];
+        for (int i = 0; i < cnt;) {
+          const int k = walk.run(cnt - i);
+          std::fill(add + i, add + i + k, (uint32_t)base + walk.value());
+          walk.advance(k);
+          i += k;
+        }
+        widen_w<true, true>(w, dst, prev, q, cnt, 0, add);
+      }
+    } else if (prev) {
+      widen_w<true>(w, dst, prev, q, cnt, (uint32_t)base);
+    } else {
+      widen_w<false>(w, dst, nullptr, q, cnt, (uint32_t)base);
+    }
     q += (int64_t)w * cnt;
   }
   return wire_align(len, 64);
@@ -290,8 +349,9 @@ int wire_decode(WireJob* job, int threads) {
 
 // ---------------------------------------------------------------- reference encoder
 namespace {
-// one segment at `out`; returns its unrounded length
-int64_t encode_seg(const char* src, const char* prev, int n, char* out) {
+// one segment at `out` (bias-coded where `walk` is given: it stands on the segment's first element);
+// returns its unrounded length
+int64_t encode_seg(const char* src, const char* prev, int n, char* out, BiasWalk* walk) {
   const int nb = (n + kWireBlock - 1) / kWireBlock;
   const int64_t hdr = wire_header_bytes(nb);
   std::memset(out, 0, (size_t)hdr);
@@ -306,6 +366,13 @@ int64_t encode_seg(const char* src, const char* prev, int n, char* out) {
       if (prev) std::memcpy(&pv, prev + 4 * ((int64_t)b * kWireBlock + i), 4);
       v[i] = (int32_t)(a - pv);
     }
+    if (walk)
+      for (int i = 0; i < cnt;) {
+        const int k = walk->run(cnt - i);
+        for (int j = i; j < i + k; ++j) v[j] = (int32_t)((uint32_t)v[j] - walk->value());
+        walk->advance(k);
+        i += k;
+      }
     const int32_t mn = *std::min_element(v, v + cnt), mx = *std::max_element(v, v + cnt);
     const uint32_t range = (uint32_t)mx - (uint32_t)mn;  // exact: mx >= mn as signed values
     const int w = range == 0 ? 0 : range <= 0xFFu ? 1 : range <= 0xFFFFu ? 2 : range <= 0xFFFFFFu ? 3 : 4;
@@ -350,14 +417,19 @@ extern "C" {
 
 int64_t tk_wire_bound(const tk_wire_record* recs, int n_recs) {
   tk::WirePlan p;
-  const int rc = tk::wire_plan(recs, n_recs, -1, "tk_wire_bound", &p);
+  const int rc = tk::wire_plan(recs, n_recs, -1, "tk_wire_bound", &p, nullptr, true);
   return rc ? rc : p.bound;
 }
 
 int64_t tk_wire_encode_host(const tk_wire_record* recs, int n_recs, const void* image, int64_t image_bytes,
                             void* wire, int64_t wire_cap) {
+  return tk_wire_encode_host_bias(recs, nullptr, n_recs, image, image_bytes, wire, wire_cap);
+}
+
+int64_t tk_wire_encode_host_bias(const tk_wire_record* recs, const tk_wire_addend* addends, int n_recs, const void* image,
+                                 int64_t image_bytes, void* wire, int64_t wire_cap) {
   tk::WirePlan p;
-  if (const int rc = tk::wire_plan(recs, n_recs, image_bytes, "tk_wire_encode_host", &p)) return rc;
+  if (const int rc = tk::wire_plan(recs, n_recs, image_bytes, "tk_wire_encode_host", &p, addends)) return rc;
   if (!image || !wire || wire_cap < p.bound) {
     tk::set_error("tk_wire_encode_host: the wire buffer is smaller than tk_wire_bound");
     return TK_ERR_INVALID_ARG;
@@ -368,14 +440,19 @@ int64_t tk_wire_encode_host(const tk_wire_record* recs, int n_recs, const void* 
   int64_t cursor = 0;
   for (size_t i = 0; i < p.segs.size(); ++i) {
     const tk::WireSegRef& s = p.segs[i];
-    const int kind = recs[s.rec].kind;
+    const int kind = tk::wire_seg_kind(recs[s.rec].kind);
     const tk::WireSegAddr a =
         tk::wire_seg_addr(s, kind, (const char*)image + recs[s.rec].offset,
                           recs[s.rec].diff ? (const char*)image + recs[s.rec - 1].offset : nullptr);
     const uint32_t start = (uint32_t)(cursor / 64);
     std::memcpy((char*)wire + 4 * i, &start, 4);
-    const int64_t len = kind == tk::kWireI32 ? tk::encode_seg(a.at, a.prev, s.n, payload + cursor)
-                                             : tk::encode_seg8(a.at, a.prev, s.n, kind, payload + cursor);
+    tk::WireSegHost bias{};
+    if (const tk_wire_addend* ad = tk::wire_addend_of(recs, addends, s.rec))
+      tk::wire_seg_bias(&bias, ad->addend, ad->plane, ad->channels, s.e0);
+    tk::BiasWalk walk(bias);
+    const int64_t len = kind == tk::kWireI32
+                            ? tk::encode_seg(a.at, a.prev, s.n, payload + cursor, bias.addend ? &walk : nullptr)
+                            : tk::encode_seg8(a.at, a.prev, s.n, kind, payload + cursor);
     const int64_t padded = tk::wire_align(len, 64);
     std::memset(payload + cursor + len, 0, (size_t)(padded - len));
     cursor += padded;
@@ -385,8 +462,13 @@ int64_t tk_wire_encode_host(const tk_wire_record* recs, int n_recs, const void* 
 
 int tk_wire_decode(const tk_wire_record* recs, int n_recs, const void* wire, int64_t wire_bytes, void* image,
                    int64_t image_bytes, int threads) {
+  return tk_wire_decode_bias(recs, nullptr, n_recs, wire, wire_bytes, image, image_bytes, threads);
+}
+
+int tk_wire_decode_bias(const tk_wire_record* recs, const tk_wire_addend* addends, int n_recs, const void* wire,
+                        int64_t wire_bytes, void* image, int64_t image_bytes, int threads) {
   tk::WirePlan p;
-  if (const int rc = tk::wire_plan(recs, n_recs, image_bytes, "tk_wire_decode", &p)) return rc;
+  if (const int rc = tk::wire_plan(recs, n_recs, image_bytes, "tk_wire_decode", &p, addends)) return rc;
   if (!wire || !image || wire_bytes < 0) {
     tk::set_error("tk_wire_decode: null buffer");
     return TK_ERR_INVALID_ARG;
@@ -397,7 +479,9 @@ int tk_wire_decode(const tk_wire_record* recs, int n_recs, const void* wire, int
     const tk::WireSegAddr a =
         tk::wire_seg_addr(s, recs[s.rec].kind, (char*)image + recs[s.rec].offset,
                           recs[s.rec].diff ? (const char*)image + recs[s.rec - 1].offset : nullptr);
-    segs[i] = {a.at, a.prev, s.n, recs[s.rec].kind};
+    segs[i] = {a.at, a.prev, s.n, tk::wire_seg_kind(recs[s.rec].kind)};
+    if (const tk_wire_addend* ad = tk::wire_addend_of(recs, addends, s.rec))
+      tk::wire_seg_bias(&segs[i], ad->addend, ad->plane, ad->channels, s.e0);
   }
   tk::WireJob job{(const char*)wire, wire_bytes, segs.data(), (int64_t)segs.size(),
                   p.units.data(), (int64_t)p.units.size()};

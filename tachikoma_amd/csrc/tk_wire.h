@@ -7,7 +7,15 @@
 // A record of n int32 elements is cut into blocks of kWireBlock elements and segments of
 // kWireSegBlocks blocks (the last block / segment of a record may be short).  The coded value of
 // an element is the element itself or, for a differenced record, element - predecessor element
-// with int32 wrap-around.  A block is coded as base (the minimum coded value) plus unsigned
+// with int32 wrap-around; a differenced record may also carry a per-channel addend (bias coding: a
+// bias_add record after its convolution), and then the coded value of element e is
+// element - predecessor element - addend[(e / plane) % channels], `plane` being the product of the
+// dims after the bias axis and `channels` the dim on it (a dense record has plane 1).  The addend is
+// a predictor: encoder and decoder are handed the same values (the packed plan snapshots the bias
+// once, a device copy for the encoder and a host copy for the decoder), any values round-trip any
+// data, and where they are the bias every block of the record is constant -- also the blocks that
+// straddle a plane boundary, which a plain difference pays 1-2 bytes per element for.  Geometry,
+// widths, table and cursor are the same with and without an addend.  A block is coded as base (the minimum coded value) plus unsigned
 // offsets of `width` bytes each, width 0..4 from the block's range in unsigned 32-bit arithmetic
 // (0: constant block, 4: raw escape).
 //
@@ -49,11 +57,21 @@ inline int64_t wire_align(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 inline int64_t wire_table_bytes(int64_t n_seg) { return wire_align(4 * n_seg, 64); }
 inline int64_t wire_header_bytes(int nb) { return wire_align(4 * (int64_t)nb, 16) + wire_align(nb, 16); }
 // element kind of a record / segment (tk_wire_record.kind)
-enum WireKind : int32_t { kWireI32 = 0, kWireI8 = 1, kWireU8 = 2 };
-inline int wire_elem_bytes(int kind) { return kind == kWireI32 ? 4 : 1; }
+enum WireKind : int32_t { kWireI32 = 0, kWireI8 = 1, kWireU8 = 2, kWireI32Bias = 3 };
+// A record of kind kWireI32Bias is an int32 record coded with an addend (tk_wire_addend); its
+// segments are int32 segments (kWireI32) that carry the addend.
+inline int wire_seg_kind(int kind) { return kind == kWireI32Bias ? (int)kWireI32 : kind; }
+inline int wire_elem_bytes(int kind) { return wire_seg_kind(kind) == kWireI32 ? 4 : 1; }
 // worst case (every block raw) of a segment of n elements of esize bytes
 inline int64_t wire_seg_bound(int n, int esize = 4) {
   return wire_align(wire_header_bytes((n + kWireBlock - 1) / kWireBlock) + esize * (int64_t)n, 64);
+}
+
+// Where a bias-coded segment starts in its record: element e0 lies in the plane of channel c0 at
+// position r0.  Computed on the host, so that the device walks a segment in 32-bit arithmetic.
+struct WireSegPos { int32_t c0, r0; };
+inline WireSegPos wire_seg_pos(int64_t e0, int32_t plane, int32_t channels) {
+  return {(int32_t)((e0 / plane) % channels), (int32_t)(e0 % plane)};
 }
 
 // device encoder's view of a segment
@@ -62,6 +80,9 @@ struct WireSegDev {
   const void* prev;  // differenced against / clamp-predicted from (device), or null
   int32_t n;
   int32_t kind;
+  const int32_t* addend = nullptr;  // bias coding (device, `channels` values), or null
+  int32_t plane = 0, channels = 0;
+  int32_t c0 = 0, r0 = 0;           // wire_seg_pos of the segment's first element
 };
 // device decoder's view (tk_wire_unpack_device): a segment's destination, and a decode unit
 struct WireSegOut {
@@ -90,6 +111,9 @@ struct WireSegHost {
   const char* prev;  // differenced against / clamp-predicted from (image bytes already present), or null
   int32_t n;
   int32_t kind;
+  const int32_t* addend = nullptr;  // bias coding (host, `channels` values), or null
+  int32_t plane = 0, channels = 0;
+  int32_t c0 = 0, r0 = 0;           // wire_seg_pos of the segment's first element
 };
 // One decoder work item: segments first, first + stride, ... (`count` of them), decoded in this
 // order by one thread: the same segment of a chain of records differenced against each other.
@@ -102,6 +126,11 @@ struct WireSegRef {
   int64_t e0;  // first element
 };
 
+// record i's addend where it has one (kind 3 and addends given), else null
+inline const tk_wire_addend* wire_addend_of(const tk_wire_record* recs, const tk_wire_addend* addends, int i) {
+  return addends && recs[i].kind == kWireI32Bias ? addends + i : nullptr;
+}
+
 // The plan of a run of records: segments, decode units (record i with `diff` is decoded after the
 // same segment of record i - 1, which has its kind and element count: differenced against it, or
 // clamp-predicted from it) and the wire buffer's size with every block raw.  Segments count elements.
@@ -112,8 +141,13 @@ struct WirePlan {
 };
 // Plans `recs` for the entry point `who`, offsets held to an image of image_bytes (-1: not looked
 // at).  An unknown kind, a record of no size or outside the image, a `diff` across a change of size
-// or kind, 2^31 segments or more: sets the error under `who`'s name and returns the status.
-int wire_plan(const tk_wire_record* recs, int n_recs, int64_t image_bytes, const char* who, WirePlan* plan);
+// or kind (kinds 0 and 3 chain with each other), a record of kind 3 that is not differenced, has
+// 2^31 elements or more, or whose addends[i] has no addend or a plane or channels below 1, 2^31
+// segments or more: sets the error under `who`'s name and returns the status.  `addends` null (every
+// entry point without addends; packed trace files, the device decoder): kind 3 is refused
+// (TK_ERR_UNSUPPORTED) unless `bias_ok` (tk_wire_bound: the size does not depend on the addend).
+int wire_plan(const tk_wire_record* recs, int n_recs, int64_t image_bytes, const char* who, WirePlan* plan,
+              const tk_wire_addend* addends = nullptr, bool bias_ok = false);
 
 // Where a segment starts in its record's buffer and in its predecessor's (a null base gives null).
 // Whether the two are chained in the decode order is the plan's `diff`: another plan may hold the predecessor.
@@ -121,6 +155,15 @@ struct WireSegAddr { char* at; const char* prev; };
 inline WireSegAddr wire_seg_addr(const WireSegRef& s, int kind, const void* base, const void* prev_base) {
   const int64_t b0 = wire_elem_bytes(kind) * s.e0;
   return {base ? (char*)base + b0 : nullptr, prev_base ? (const char*)prev_base + b0 : nullptr};
+}
+
+// The bias coding of a segment (WireSegDev / WireSegHost) that starts at element e0 of a record
+// coded with `addend` (null: none), which whoever reads the segment's sources can read.
+template <typename Seg>
+inline void wire_seg_bias(Seg* s, const int32_t* addend, int32_t plane, int32_t channels, int64_t e0) {
+  if (!addend) return;
+  const WireSegPos at = wire_seg_pos(e0, plane, channels);
+  s->addend = addend, s->plane = plane, s->channels = channels, s->c0 = at.c0, s->r0 = at.r0;
 }
 
 // Unrounded length of a segment of n elements of `kind` placed at table entry `start`, from the

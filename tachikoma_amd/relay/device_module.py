@@ -1105,7 +1105,8 @@ class DeviceModule:
         """Trace wire of the packed capture: int32 records cross the link narrowed and are widened
         on the host, clip records cross as clamps of the record before them and are rebuilt there
         (tk_module_set_trace_wire; on by default, TK_TRACE_WIRE=0 forces it off, TK_WIRE_CLAMP=0
-        at module creation keeps the clip records raw)."""
+        at module creation keeps the clip records raw, TK_WIRE_BIAS=0 the bias_add records plain
+        differences from their convolution)."""
         _lib.check(self.lib.tk_module_set_trace_wire(self.handle, int(enable)), "tk_module_set_trace_wire")
 
     def wire_stats(self) -> List[dict]:

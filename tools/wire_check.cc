@@ -223,6 +223,106 @@ static void byte_cases(int n) {
   }
 }
 
+// Bias coding: a chain a, a + bias1[c], a + bias1[c] + bias2[c], ... of `planes * channels * samples`
+// elements, every record after the first coded with its addend, the addends in heap buffers of
+// exactly `channels` elements.  `junk`: the last record is noise instead (the prediction fails).
+// Returns the wire bytes; *flat: those of the same chain if every coded block were constant.
+static int64_t bias_roundtrip(int plane, int channels, int samples, const std::vector<Rec>& biases, bool junk, int threads,
+                              int64_t* flat) {
+  const int64_t n = (int64_t)plane * channels * samples;
+  const int k = 1 + (int)biases.size();
+  std::vector<Rec> recs(k, Rec(n));
+  recs[0] = span((int)n, -60000, 120000);
+  std::vector<std::unique_ptr<int32_t[]>> addends;
+  for (int m = 1; m < k; ++m) {
+    addends.emplace_back(new int32_t[channels]);
+    std::memcpy(addends.back().get(), biases[m - 1].data(), 4 * (size_t)channels);
+    for (int64_t e = 0; e < n; ++e)
+      recs[m][e] = junk && m == k - 1 ? (int32_t)g_rng()
+                                      : (int32_t)((uint32_t)recs[m - 1][e] + (uint32_t)biases[m - 1][(e / plane) % channels]);
+  }
+  std::vector<tk_wire_record> r(k);
+  std::vector<tk_wire_addend> ad(k);
+  int64_t at = 3;
+  for (int m = 0; m < k; ++m) {
+    r[m] = {at, n, m > 0, m ? 3 : 0};
+    ad[m] = {m ? plane : 0, m ? channels : 0, m ? addends[m - 1].get() : nullptr};
+    at += 4 * n + 5;
+  }
+  const int64_t total = at;
+  std::unique_ptr<uint8_t[]> src(new uint8_t[total]), out(new uint8_t[total]);
+  std::memset(src.get(), 0xA5, total);
+  for (int m = 0; m < k; ++m) std::memcpy(src.get() + r[m].offset, recs[m].data(), 4 * n);
+  std::memcpy(out.get(), src.get(), total);
+  for (int m = 0; m < k; ++m) std::memset(out.get() + r[m].offset, 0, 4 * n);
+  const int64_t bound = tk_wire_bound(r.data(), k);
+  CHECK(bound > 0);
+  if (bound <= 0) return bound;
+  std::unique_ptr<uint8_t[]> big(new uint8_t[bound]);
+  const int64_t nb = tk_wire_encode_host_bias(r.data(), ad.data(), k, src.get(), total, big.get(), bound);
+  CHECK(nb > 0 && nb <= bound);
+  if (nb <= 0) return nb;
+  std::unique_ptr<uint8_t[]> wire(new uint8_t[nb]);
+  std::memcpy(wire.get(), big.get(), nb);
+  CHECK(tk_wire_decode_bias(r.data(), ad.data(), k, wire.get(), nb, out.get(), total, threads) == 0 &&
+        std::memcmp(out.get(), src.get(), total) == 0);
+  // packed trace files do not code addends, and the entry points without addends cannot: all
+  // refuse the bias-coded records
+  CHECK(tk_wire_check(r.data(), k, wire.get(), nb) == TK_ERR_UNSUPPORTED);
+  CHECK(tk_wire_decode(r.data(), k, wire.get(), nb, out.get(), total, threads) == TK_ERR_UNSUPPORTED);
+  CHECK(tk_wire_encode_host(r.data(), k, src.get(), total, big.get(), bound) == TK_ERR_UNSUPPORTED);
+  // the first record alone, then headers only for each record after it
+  int64_t first = 0, hdrs = 0, n_seg = 0;
+  {
+    tk_wire_record r0 = r[0];
+    first = tk_wire_encode_host(&r0, 1, src.get(), total, big.get(), bound);
+    for (int64_t e = 0; e < n; e += tk::kWireSegElems, ++n_seg)
+      hdrs += tk::wire_align(tk::wire_header_bytes((int)((std::min<int64_t>(tk::kWireSegElems, n - e) + 255) / 256)), 64);
+    first -= tk::wire_table_bytes(n_seg);
+  }
+  *flat = tk::wire_table_bytes(k * n_seg) + first + (k - 1) * hdrs;
+  return nb;
+}
+
+static void bias_cases() {
+  auto bias = [](int channels, int64_t scale) {
+    Rec b(channels);
+    for (int c = 0; c < channels; ++c) b[c] = (int32_t)((c * 7919 % channels) * scale - 30000);
+    return b;
+  };
+  int64_t flat = 0;
+  for (int threads : {1, 0}) {
+    // 7x7 planes, where every block straddles: the pair costs its headers alone
+    CHECK(bias_roundtrip(49, 24, 2, {bias(24, 1013)}, false, threads, &flat) == flat);
+    // a plane longer than a segment: segments 1 and 2 start mid-plane; a ragged last block
+    CHECK(bias_roundtrip(16385, 2, 1, {bias(2, 999)}, false, threads, &flat) == flat);
+    // dense (plane 1), and planes below a lane's 16 elements
+    CHECK(bias_roundtrip(1, 10, 5, {bias(10, 31)}, false, threads, &flat) == flat);
+    CHECK(bias_roundtrip(3, 5, 40, {bias(5, 31)}, false, threads, &flat) == flat);
+    // a chain of three with addends at both ends of int32: sums and differences wrap
+    CHECK(bias_roundtrip(196, 4, 3, {{INT_MIN, INT_MAX, -1, 0}, {INT_MAX, INT_MAX, INT_MIN, 5}}, false, threads, &flat) == flat);
+    // the prediction fails everywhere: still round-trips, at the raw width
+    CHECK(bias_roundtrip(49, 24, 20, {bias(24, 1013), bias(24, 77)}, true, threads, &flat) >= flat + 4 * 49 * 24 * 20);
+  }
+  // a bias-coded record that is not differenced, follows a 1-byte record, or lacks its geometry
+  const int32_t one[1] = {1};
+  tk_wire_record bad[2] = {{0, 8, 0, 0}, {32, 8, 1, 3}};
+  tk_wire_addend ad[2] = {{0, 0, nullptr}, {1, 1, one}};
+  uint8_t image[64] = {0}, wire[1024];
+  auto encode = [&] { return tk_wire_encode_host_bias(bad, ad, 2, image, 64, wire, sizeof(wire)); };
+  CHECK(tk_wire_bound(bad, 2) > 0 && tk_wire_bound(bad, 2) <= (int64_t)sizeof(wire) && encode() > 0);
+  bad[1].diff = 0;
+  CHECK(tk_wire_bound(bad, 2) == TK_ERR_INVALID_ARG && encode() == TK_ERR_INVALID_ARG);
+  bad[1].diff = 1, ad[1].plane = 0;
+  CHECK(encode() == TK_ERR_INVALID_ARG);
+  ad[1].plane = 1, ad[1].channels = 0;
+  CHECK(encode() == TK_ERR_INVALID_ARG);
+  ad[1].channels = 1, ad[1].addend = nullptr;
+  CHECK(encode() == TK_ERR_INVALID_ARG);
+  ad[1].addend = one, bad[0].kind = 1;
+  CHECK(tk_wire_bound(bad, 2) == TK_ERR_INVALID_ARG && encode() == TK_ERR_INVALID_ARG);
+}
+
 // tk::wire_plan refuses `r` with `status`, under the caller's name
 static bool refused(const std::vector<tk_wire_record>& r, int64_t image_bytes, int status = TK_ERR_INVALID_ARG) {
   tk::WirePlan p;
@@ -295,7 +395,8 @@ static void planner_cases() {
   CHECK(refused({{0, 8, 0, 1}, {8, 8, 1, 2}}, -1));                    // ... of kind
   CHECK(refused({{0, 0, 0, 0}}, -1));                                  // no elements
   CHECK(refused({{0, ((int64_t)1 << 40) + 1, 0, 1}}, -1));             // too many
-  CHECK(refused({{0, 8, 0, 3}}, -1) && refused({{0, 8, 0, -1}}, -1));  // unknown kinds
+  CHECK(refused({{0, 8, 0, 4}}, -1) && refused({{0, 8, 0, -1}}, -1));  // unknown kinds
+  CHECK(refused({{0, 8, 0, 0}, {32, 8, 1, 3}}, -1, TK_ERR_UNSUPPORTED));   // bias-coded, and no addends taken
   CHECK(refused({{-1, 8, 0, 0}}, -1) && refused({{-1, 8, 0, 0}}, 64));
   CHECK(refused({{65, 8, 0, 1}}, 64));                                 // an offset outside the image
   CHECK(refused({{36, 8, 0, 0}}, 64) && !refused({{32, 8, 0, 0}}, 64));  // an extent outside it
@@ -306,6 +407,7 @@ static void planner_cases() {
 
 int main() {
   planner_cases();
+  bias_cases();
   for (int n : {1, 15, 16, 17, 255, 256, 257, 3 * 256 + 17, 2 * 16384 + 300}) byte_cases(n);
   const int sizes[] = {1, 255, 256, 257, 3 * 256 + 17, 2 * 16384 + 300};
   for (int n : sizes) {
