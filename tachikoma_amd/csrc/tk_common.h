@@ -6,12 +6,11 @@
 
 #include <string>
 
-#include "../../include/tachikoma.h"
+#include "tk_tensor.h"
 
 namespace tk {
 
-// ---------------------------------------------------------------- errors
-void set_error(const std::string& msg);
+// ---------------------------------------------------------------- errors (set_error: tk_tensor.h)
 
 #define TK_CHECK_ARG(cond, msg)                         \
   do {                                                  \
@@ -39,31 +38,7 @@ void set_error(const std::string& msg);
     }                                                                                 \
   } while (0)
 
-// ---------------------------------------------------------------- tensors
-inline int64_t numel(const tk_tensor* t) {
-  int64_t n = 1;
-  for (int i = 0; i < t->ndim; ++i) n *= t->shape[i];
-  return n;
-}
-inline int elem_bytes(const tk_tensor* t) { return (t->dtype.bits + 7) / 8; }
-inline int64_t nbytes(const tk_tensor* t) { return numel(t) * elem_bytes(t); }
-inline char* ptr(const tk_tensor* t) { return static_cast<char*>(t->data) + t->byte_offset; }
-inline bool is_int(const tk_tensor* t, int bits) {
-  return t->dtype.code == TK_DL_INT && t->dtype.bits == bits && t->dtype.lanes == 1;
-}
-inline bool is_uint(const tk_tensor* t, int bits) {
-  return t->dtype.code == TK_DL_UINT && t->dtype.bits == bits && t->dtype.lanes == 1;
-}
-inline bool is_int8ish(const tk_tensor* t) { return is_int(t, 8) || is_uint(t, 8); }
-inline bool is_integer(const tk_tensor* t) {
-  return (t->dtype.code == TK_DL_INT || t->dtype.code == TK_DL_UINT) && t->dtype.lanes == 1 &&
-         (t->dtype.bits == 8 || t->dtype.bits == 16 || t->dtype.bits == 32 || t->dtype.bits == 64);
-}
-inline bool is_f32(const tk_tensor* t) {
-  return t->dtype.code == TK_DL_FLOAT && t->dtype.bits == 32 && t->dtype.lanes == 1;
-}
-inline bool compact(const tk_tensor* t) { return t->strides == nullptr; }
-
+// ---------------------------------------------------------------- tensors (helpers: tk_tensor.h)
 // dtype id used as a template switch in kernels
 enum DT { DT_I8 = 0, DT_U8 = 1, DT_I16 = 2, DT_U16 = 3, DT_I32 = 4, DT_U32 = 5, DT_I64 = 6, DT_U64 = 7 };
 inline int dt_of(const tk_tensor* t) {

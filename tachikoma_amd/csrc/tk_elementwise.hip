@@ -6,15 +6,9 @@
 // (SURVEY.md Appendix A); every function cites the reference lowering it mirrors.
 #include <algorithm>
 
-#include "tk_common.h"
+#include "tk_ops.h"  // also the float32 variants of the shared ops (tk_realize.hip)
 
 namespace tk {
-
-// float32 variants of the shared ops (relay.quantize-realized graphs, tk_realize.hip)
-int cast_f32_impl(const tk_tensor* x, tk_tensor* y, hipStream_t s);
-int bias_add_f32_impl(const tk_tensor* x, const tk_tensor* b, tk_tensor* y, int axis, hipStream_t s);
-int global_avg_pool_f32_impl(const tk_tensor* x, tk_tensor* y, hipStream_t s);
-int max_pool_f32_impl(const tk_tensor* x, tk_tensor* y, const tk_pool2d_attrs* a, hipStream_t s);
 
 constexpr int kBlock = 256;
 

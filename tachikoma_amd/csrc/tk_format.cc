@@ -19,11 +19,7 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/tachikoma.h"
-
-namespace tk {
-void set_error(const std::string& msg);
-}
+#include "tk_tensor.h"
 
 namespace {
 

@@ -23,6 +23,7 @@
 #include <cstring>
 
 #include "tk_conv.h"
+#include "tk_ops.h"
 
 namespace tk {
 

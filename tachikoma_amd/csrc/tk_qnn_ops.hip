@@ -11,7 +11,7 @@
 #include <algorithm>
 #include <climits>
 
-#include "tk_common.h"
+#include "tk_ops.h"
 
 #pragma clang fp contract(off)
 

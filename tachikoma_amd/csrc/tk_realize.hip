@@ -13,7 +13,7 @@
 #include <cmath>
 #include <limits>
 
-#include "tk_common.h"
+#include "tk_ops.h"
 
 // hipcc contracts a*b+c into FMA by default (the __fmul_rn/__fadd_rn helpers included, once
 // inlined); the fixed order above means one rounding per multiply and per add

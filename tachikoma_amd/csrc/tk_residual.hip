@@ -16,7 +16,7 @@
 // (tk_conv2d_make_shadow layout); channels >= C are written as 0.
 #include <algorithm>
 
-#include "tk_common.h"
+#include "tk_ops.h"
 
 namespace tk {
 

@@ -7,80 +7,19 @@
 // flat node list on one HIP stream and, when asked, copies every node output to
 // host memory on a second stream, each copy gated by an event recorded right
 // after the node, so the PCIe transfer of node i overlaps the kernels of nodes > i.
+// The packed capture, tk_module_run_graph's default way of copying, is tk_capture.cc.
 #include <algorithm>
-#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <map>
 #include <memory>
-#include <mutex>
 #include <string>
 #include <vector>
 
 #include "tk_chain.h"
-#include "tk_common.h"
-#include "tk_wire.h"
+#include "tk_module.h"
 
 namespace tk {
-int requantize_impl(const tk_tensor* x, tk_tensor* y, const tk_requantize_attrs* a, hipStream_t s);
-int bias_add_impl(const tk_tensor* x, const tk_tensor* b, tk_tensor* y, int axis, hipStream_t s);
-int clip_impl(const tk_tensor* x, tk_tensor* y, int64_t lo, int64_t hi, hipStream_t s);
-int cast_impl(const tk_tensor* x, tk_tensor* y, hipStream_t s);
-int qnn_add_impl(const tk_tensor* a, const tk_tensor* b, tk_tensor* y, const tk_qnn_add_attrs* at, hipStream_t s);
-int add_block_impl(const tk_tensor* a, const tk_tensor* b, tk_tensor* const* outs, int n_outs,
-                   const tk_add_block_attrs* at, void* shadow, hipStream_t s);
-int max_pool_impl(const tk_tensor* x, tk_tensor* y, const tk_pool2d_attrs* a, hipStream_t s);
-int max_pool_shadow_impl(const tk_tensor* x, const void* x_shadow, tk_tensor* y, const tk_pool2d_attrs* a,
-                         void* y_shadow, hipStream_t s);
-int avg_pool_impl(const tk_tensor* x, tk_tensor* y, const tk_pool2d_attrs* a, hipStream_t s);
-int global_avg_pool_impl(const tk_tensor* x, tk_tensor* y, hipStream_t s);
-int copy_impl(const tk_tensor* x, tk_tensor* y, hipStream_t s);
-int pad_impl(const tk_tensor* x, tk_tensor* y, const tk_pad_attrs* a, hipStream_t s);
-int postops_impl(const tk_tensor* acc, const tk_tensor* sum_src, tk_tensor* y, const tk_postops_attrs* a,
-                 hipStream_t s);
-// tk_trace.hip: what the packed capture launches
-int host_copy_impl(const void* const* src, void* const* dst, const int64_t* bytes, int n, hipStream_t s);
-int pack_records_impl(const void* table, int nrec, int64_t blocks, void* mirror, hipStream_t s);
-int wire_encode_impl(const WireSegDev* segs, int64_t n_seg, uint32_t* cursor, void* wire, int64_t wire_bytes,
-                     hipStream_t s);
-int ewise_impl(const tk_tensor* x, const tk_tensor* r, tk_tensor* y, const tk_ewise_attrs* a, hipStream_t s);
-int conv2d_f32_impl(const tk_tensor* x, const tk_tensor* w, tk_tensor* y, const tk_conv2d_attrs* a, hipStream_t s);
-int dense_f32_impl(const tk_tensor* x, const tk_tensor* w, tk_tensor* y, hipStream_t s);
-int64_t conv_packed_weight_bytes(const tk_tensor* weight, int groups);
-int conv_pack_weight(const tk_tensor* weight, int groups, void* packed, int32_t* sums, hipStream_t s);
-int64_t conv_shadow_bytes(const tk_tensor* data);
-int64_t conv_scratch_bytes(const tk_tensor* data, const tk_tensor* weight, const tk_conv2d_attrs* a, int block);
-int make_shadow_impl(const tk_tensor* data, void* shadow, hipStream_t s);
-int conv2d_prepared_impl(const tk_tensor* data, const void* shadow, const tk_tensor* weight, const void* packed,
-                         const int32_t* sums, tk_tensor* out, const tk_conv2d_attrs* a, void* scratch, hipStream_t s);
-int64_t conv2d_workspace_bytes(const tk_tensor* data, const tk_tensor* weight, const tk_conv2d_attrs* a);
-int conv2d_impl(const tk_tensor* data, const tk_tensor* weight, tk_tensor* out, const tk_conv2d_attrs* a,
-                void* workspace, hipStream_t s);
-int64_t dense_workspace_bytes(const tk_tensor* data, const tk_tensor* weight);
-int dense_impl(const tk_tensor* data, const tk_tensor* weight, tk_tensor* out, const tk_dense_attrs* a,
-               void* workspace, hipStream_t s);
-int conv2d_block_impl(const tk_tensor* data, const void* shadow, const tk_tensor* weight, const void* packed,
-                      const int32_t* sums, const tk_tensor* bias, tk_tensor* const* outs, int n_outs,
-                      const tk_block_attrs* attrs, void* scratch, void* shadow_out, hipStream_t s);
-int dense_block_impl(const tk_tensor* data, const tk_tensor* weight, const tk_tensor* bias, tk_tensor* const* outs,
-                     int n_outs, const tk_block_attrs* attrs, void* workspace, hipStream_t s);
-int qnn_quantize_impl(const tk_tensor* x, tk_tensor* y, const tk_qparams_attrs* a, hipStream_t s);
-int qnn_dequantize_impl(const tk_tensor* x, tk_tensor* y, const tk_qparams_attrs* a, hipStream_t s);
-int qnn_binary_impl(const tk_tensor* a, const tk_tensor* b, tk_tensor* y, const tk_qnn_binary_attrs* at,
-                    hipStream_t s);
-int qnn_concatenate_impl(const tk_tensor* const* xs, int n_in, tk_tensor* y, const tk_concat_attrs* a,
-                         hipStream_t s);
-int transpose_impl(const tk_tensor* x, tk_tensor* y, const tk_transpose_attrs* a, hipStream_t s);
-int conv2d_block_algos_impl(const tk_tensor* data, const tk_tensor* weight, const tk_block_attrs* attrs,
-                            int32_t* algos, int max_algos);
-int qnn_leaky_relu_impl(const tk_tensor* x, tk_tensor* y, const tk_leaky_relu_attrs* a, hipStream_t s);
-int qnn_simulated_impl(bool quant, const tk_tensor* x, tk_tensor* y, const tk_simq_attrs* a, hipStream_t s);
-int requantize_fp_impl(const tk_tensor* x, tk_tensor* y, const tk_requantize_fp_attrs* a, hipStream_t s);
-int qnn_binary_fp_impl(const tk_tensor* a, const tk_tensor* b, tk_tensor* y, const tk_qnn_binary_fp_attrs* at,
-                       hipStream_t s);
-int qnn_lookup_impl(const tk_tensor* x, tk_tensor* y, const void* table, hipStream_t s);
-int qnn_conv2d_transpose_impl(const tk_tensor* x, const tk_tensor* w, tk_tensor* y, const tk_conv2d_transpose_attrs* a,
-                              hipStream_t s);
 
 // qnn.batch_matmul (src/relay/qnn/op/batch_matmul.cc:162-228): the qnn.dense kernel per batch entry,
 // on [M, K] / [N, K] / [M, N] views of x[b], y[b] (b or 0 where that operand's batch is 1), out[b];
@@ -123,38 +62,8 @@ int batch_matmul_impl(const tk_tensor* x, const tk_tensor* y, tk_tensor* out, co
   }
   return TK_OK;
 }
-int conv2d_block_algo_info_impl(const tk_tensor* data, const tk_tensor* weight, const tk_block_attrs* attrs, int algo,
-                                char* buf, int len);
 
-// run_packed's "nothing to capture, run the plain graph" answer (not an error code)
-constexpr int TK_OK_RUN = 1;
-
-// A tensor descriptor owned by the module (shape copied).
-struct OwnedTensor {
-  tk_tensor t{};
-  std::vector<int64_t> shape;
-  void assign(const tk_tensor* src) {
-    t = *src;
-    shape.assign(src->shape, src->shape + src->ndim);
-    t.shape = shape.data();
-    t.strides = nullptr;
-  }
-  OwnedTensor() = default;
-  OwnedTensor(const OwnedTensor& o) { assign(&o.t); }
-  OwnedTensor& operator=(const OwnedTensor& o) {
-    assign(&o.t);
-    return *this;
-  }
-};
-
-struct Node {
-  tk_node desc{};
-  OwnedTensor in[TK_MAX_NODE_INPUTS];
-  OwnedTensor out[TK_MAX_NODE_OUTPUTS];
-  tk_tensor* outp[TK_MAX_NODE_OUTPUTS] = {};
-};
-
-static int run_node(Node& n, hipStream_t s) {
+int run_node(Node& n, hipStream_t s) {
   const tk_node& d = n.desc;
   const tk_tensor* i0 = &n.in[0].t;
   const tk_tensor* i1 = &n.in[1].t;
@@ -244,189 +153,6 @@ static int run_node(Node& n, hipStream_t s) {
 }
 
 }  // namespace tk
-
-// Packed trace capture for tk_module_run_graph (the default graph copy mode): the node outputs that
-// have host destinations are gathered, chunk by chunk, into a device mirror of the host image range
-// they span (header bytes included, loaded once from the host image), and each chunk is copied to
-// host memory by ONE host-issued hipMemcpyAsync gated on an event recorded after the graph that
-// ends with the chunk's pack kernel (one graph per chunk).  Two mirrors alternate between runs, so a run's kernels overlap the previous
-// run's copies (only the pack into a mirror waits for that mirror's last copies).
-struct PackRecHost {
-  const void* src;
-  int64_t dst, bytes, first_blk;
-};
-struct PackPlan {
-  std::vector<void*> dst;         // host_dst this plan was built for (the cache key)
-  char* host_lo = nullptr;        // mirrored host range [host_lo, host_lo + span)
-  int64_t span = 0;
-  void* mirror[2] = {nullptr, nullptr};
-  struct Chunk {
-    int after_node;               // pack + event after this node
-    int64_t off, len;             // mirror range copied to host_lo + off
-    int64_t table_off;            // first entry in `table`
-    int n_rec;
-    int64_t blocks;
-  };
-  std::vector<Chunk> chunks;
-  void* table = nullptr;          // device PackRec entries of every chunk
-  std::vector<hipEvent_t> ev[2];  // per chunk, recorded after its graph
-  hipEvent_t mirror_done[2] = {nullptr, nullptr};
-  bool mirror_used[2] = {false, false};
-  std::vector<hipGraph_t> g[2];   // per mirror: one graph per chunk (+ a tail graph)
-  std::vector<hipGraphExec_t> ge[2];
-  int next = 0;
-  // Trace wire (tk_module_set_trace_wire): the int32 records of a chunk, and its 1-byte records that
-  // are clips of the record before them, are not packed; an encode kernel writes them into a pinned
-  // slot and a host function widens the slot into the image.
-  bool wire = false;
-  struct Range {
-    int64_t off, len;
-  };
-  struct WireCall {  // what one decode host function works on
-    tk::WireJob job;
-    std::atomic<int>* failed = nullptr;
-  };
-  struct WireChunk {
-    std::vector<Range> raw;  // mirror ranges of the records that are not coded (runs of adjacent ones)
-    int64_t seg_off = 0;     // first entry in `wire_segs`
-    int64_t coded_bytes = 0, bound = 0;
-    std::vector<tk::WireSegHost> segs;
-    std::vector<tk::WireUnit> units;
-    std::unique_ptr<WireCall[]> calls;  // one per slot
-    hipEvent_t landed = nullptr;        // the chunk's wire work is done
-    int last_slot = -1;
-  };
-  std::vector<WireChunk> wchunks;
-  void* wire_segs = nullptr;   // device WireSegDev entries of every chunk
-  // Bias coding: the bias vectors of the records coded with an addend, copied once when the plan
-  // is built.  The encoder subtracts the device copy and the decoder adds the host copy, which is
-  // a copy of that device copy; neither reads a node's live bias, so new parameters can make the
-  // prediction worse but never the two sides disagree.
-  int32_t* addend_dev = nullptr;
-  std::vector<int32_t> addend_host;
-  std::vector<void*> slots;    // pinned ring of worst-case-sized chunk slots
-  uint32_t* cursors = nullptr; // device, one per slot
-  std::vector<hipEvent_t> slot_done;  // decode of the slot's last use (decode stream)
-  std::vector<char> slot_used;
-  int slot_next = 0;
-  ~PackPlan() {
-    for (auto& w : wchunks)
-      if (w.landed) (void)hipEventDestroy(w.landed);
-    for (auto e : slot_done) (void)hipEventDestroy(e);
-    for (void* p : slots) (void)hipHostFree(p);
-    if (wire_segs) (void)hipFree(wire_segs);
-    if (addend_dev) (void)hipFree(addend_dev);
-    if (cursors) (void)hipFree(cursors);
-    for (int m = 0; m < 2; ++m) {
-      for (auto x : ge[m]) (void)hipGraphExecDestroy(x);
-      for (auto x : g[m]) (void)hipGraphDestroy(x);
-      for (auto e : ev[m]) (void)hipEventDestroy(e);
-      if (mirror_done[m]) (void)hipEventDestroy(mirror_done[m]);
-      if (mirror[m]) (void)hipFree(mirror[m]);
-    }
-    if (table) (void)hipFree(table);
-  }
-};
-
-struct tk_module {
-  std::vector<tk::Node> nodes;
-  std::vector<hipEvent_t> done;  // one per node, recorded after it on the compute stream
-  std::vector<hipEvent_t> prof;  // n+1 timing events for run_profiled / profiling mode
-  // Recorded on the capture stream after the last D2H copy of a traced run.  Every later
-  // run (and, through tk_module_wait_capture, every input write) first makes its stream wait
-  // on it: the copies read the module's buffers, so overwriting them before the copies land
-  // would mix two runs in one trace image (write-after-read across streams).
-  hipEvent_t capture_done = nullptr;
-  bool capture_recorded = false;
-  bool capture_plain = false;  // the last capture copied from the record buffers themselves
-  bool profiling = false;
-  bool have_times = false;
-  // tk_module_run_graph: the whole run (every node, and the copies when capturing) as one HIP
-  // graph per (stream, capture stream, host destinations), instantiated once and replayed; a few
-  // are kept (a file sink alternates two trace images)
-  struct Graph {
-    hipGraph_t g = nullptr;
-    hipGraphExec_t ge = nullptr;
-    hipStream_t s = nullptr, cs = nullptr;
-    std::vector<void*> dst;
-  };
-  std::vector<Graph> graphs;
-  hipEvent_t graph_join = nullptr, graph_pre = nullptr;
-  // the graphs are captured on two streams of the module's own (the caller's may be the legacy
-  // default stream, which cannot capture) and launched on the caller's
-  hipStream_t cap_s = nullptr, cap_cs = nullptr, cap_cx[3] = {nullptr, nullptr, nullptr};
-  // graph copies as copy kernels instead of memcpy nodes: measured slower (41.7 vs 52.7 GB/s per
-  // traced ResNet-50 step, profiles/r03n_run_modes.txt), so off by default
-  bool graph_copy_kernels = false;
-  // memcpy nodes in this many parallel chains (1..4): 4 measured 53.4 GB/s per traced ResNet-50
-  // step against 52.7 for one chain (profiles/r03s_graph_copy_chains.txt)
-  int graph_copy_chains = 4;
-  // packed capture (default): records gathered into device mirrors, copied in this many chunks
-  bool graph_packed = true;
-  int pack_chunks = 8;
-  std::vector<std::unique_ptr<PackPlan>> packs;
-  // copy trace of packed runs (tk_module_set_copy_trace): a timing event on the compute stream
-  // before the run's first launch, and two per chunk on the capture stream around its copy
-  bool copy_trace = false;
-  hipEvent_t ct_t0 = nullptr;
-  std::vector<hipEvent_t> ct_ev;
-  std::vector<int64_t> ct_bytes;
-  // trace wire of the packed capture: on unless TK_TRACE_WIRE=0 was set when the module was
-  // created; wire traffic and decodes run on two streams of the module's own
-  // TK_WIRE_CLAMP=0 at creation keeps the clip records raw (the same library's comparison run)
-  // TK_WIRE_BIAS=0 at creation keeps the bias_add records plain differences (likewise)
-  bool trace_wire = true, wire_forced_off = false, wire_clamp = true, wire_bias = true;
-  hipStream_t wire_s = nullptr, dec_s = nullptr;
-  hipEvent_t wire_tail = nullptr, decode_tail = nullptr;  // last wire work / decode of the last wire run
-  bool wire_tail_used = false;
-  std::atomic<int> wire_failed{0};
-  PackPlan* last_wire_plan = nullptr;
-  // chain check (tk_module_check_chains): the table of the module's fused chains, laid out on the
-  // first call and kept on the device with its report, so later calls upload nothing
-  struct Chains {
-    bool built = false;
-    std::vector<tk_chain_op> ops;  // one per report entry: node order, then chain order
-    int n_chains = 0;
-    int64_t blocks = 0;
-    void* dev = nullptr;  // ChainDev[n_chains] | tk_wire_mismatch[ops.size()]
-    tk_wire_mismatch* report = nullptr;
-  } chains;
-  void drop_graph() {
-    last_wire_plan = nullptr;
-    for (Graph& x : graphs) {
-      if (x.ge) (void)hipGraphExecDestroy(x.ge);
-      if (x.g) (void)hipGraphDestroy(x.g);
-    }
-    graphs.clear();
-    if (!packs.empty()) (void)hipDeviceSynchronize();  // their mirrors may still be copied from
-    packs.clear();
-  }
-  ~tk_module() {
-    drop_graph();
-    if (chains.dev) (void)hipFree(chains.dev);
-    for (auto e : done) (void)hipEventDestroy(e);
-    for (auto e : prof) (void)hipEventDestroy(e);
-    if (capture_done) (void)hipEventDestroy(capture_done);
-    if (graph_join) (void)hipEventDestroy(graph_join);
-    if (graph_pre) (void)hipEventDestroy(graph_pre);
-    if (ct_t0) (void)hipEventDestroy(ct_t0);
-    for (auto e : ct_ev) (void)hipEventDestroy(e);
-    if (wire_tail) (void)hipEventDestroy(wire_tail);
-    if (decode_tail) (void)hipEventDestroy(decode_tail);
-    if (wire_s) (void)hipStreamDestroy(wire_s);
-    if (dec_s) (void)hipStreamDestroy(dec_s);
-    if (cap_s) (void)hipStreamDestroy(cap_s);
-    if (cap_cs) (void)hipStreamDestroy(cap_cs);
-    for (hipStream_t x : cap_cx)
-      if (x) (void)hipStreamDestroy(x);
-  }
-};
-
-// The stream about to write the module's buffers waits for the last traced run's copies.
-static int wait_capture(tk_module* mod, hipStream_t s) {
-  if (mod->capture_recorded) TK_HIP(hipStreamWaitEvent(s, mod->capture_done, 0));
-  return TK_OK;
-}
 
 extern "C" {
 
@@ -592,17 +318,15 @@ int tk_module_create(const tk_node* nodes, int n_nodes, tk_module** out) {
     for (int k = 0; k < TK_MAX_NODE_OUTPUTS; ++k) n.outp[k] = &n.out[k].t;
   mod->done.resize(n_nodes);
   for (int i = 0; i < n_nodes; ++i) {
-    hipError_t e = hipEventCreateWithFlags(&mod->done[i], hipEventDisableTiming);
+    hipError_t e = hipEventCreateWithFlags(mod->done[i].put(), hipEventDisableTiming);
     if (e != hipSuccess) {
-      mod->done.resize(i);
       tk::set_error(std::string("tk_module_create: hipEventCreate failed: ") + hipGetErrorString(e));
       return TK_ERR_HIP;
     }
   }
   {
-    hipError_t e = hipEventCreateWithFlags(&mod->capture_done, hipEventDisableTiming);
+    hipError_t e = hipEventCreateWithFlags(mod->capture_done.put(), hipEventDisableTiming);
     if (e != hipSuccess) {
-      mod->capture_done = nullptr;
       tk::set_error(std::string("tk_module_create: hipEventCreate failed: ") + hipGetErrorString(e));
       return TK_ERR_HIP;
     }
@@ -620,9 +344,9 @@ int tk_module_num_nodes(const tk_module* mod) { return mod ? (int)mod->nodes.siz
 
 static int ensure_prof_events(tk_module* mod) {
   while (mod->prof.size() < mod->nodes.size() + 1) {
-    hipEvent_t e;
-    TK_HIP(hipEventCreate(&e));
-    mod->prof.push_back(e);
+    tk::OwnedEvent e;
+    TK_HIP(hipEventCreate(e.put()));
+    mod->prof.push_back(std::move(e));
   }
   return TK_OK;
 }
@@ -700,7 +424,7 @@ int tk_module_run(tk_module* mod, void* stream, void* capture_stream, void* cons
   hipStream_t s = tk::as_stream(stream);
   hipStream_t cs = tk::as_stream(capture_stream);
   bool capture = capture_stream && host_dst;
-  int rc0 = wait_capture(mod, s);
+  int rc0 = tk::wait_capture(mod, s);
   if (rc0) return rc0;
   rc0 = enqueue_nodes(mod, s, cs, host_dst, capture, mod->profiling);
   if (rc0) return rc0;
@@ -730,552 +454,6 @@ int tk_module_set_graph_copies(tk_module* mod, int copy_kernels) {
   return TK_OK;
 }
 
-int tk_module_set_trace_chunks(tk_module* mod, int chunks) {
-  if (!mod || chunks < 1 || chunks > 256) {
-    tk::set_error("tk_module_set_trace_chunks: chunks must be 1..256");
-    return TK_ERR_INVALID_ARG;
-  }
-  if (mod->pack_chunks != chunks) mod->drop_graph();
-  mod->pack_chunks = chunks;
-  return TK_OK;
-}
-
-// The steps of build_pack_plan.  A record of the plan: a node output that has a host destination.
-struct PackRecord {
-  char* host;
-  const void* src;
-  int64_t bytes;
-  int node, out;
-  const tk_tensor* t;
-  bool wire, diff;  // coded on the wire; as the difference from the record before it
-  bool clamp;       // coded on the wire as a clamp of the record before it (1-byte)
-  // a differenced record that is the bias_add of the record before it: the bias vector, the
-  // geometry of its axis and where its snapshot lies in the plan's addend buffers (int32 elements)
-  const tk_tensor* bias = nullptr;
-  int32_t plane = 0, channels = 0;
-  int64_t addend_at = 0;
-};
-
-// the records in host order; overlapping destinations are refused
-static int collect_records(const tk_module* mod, const std::vector<void*>& dst, std::vector<PackRecord>* recs) {
-  for (size_t i = 0; i < mod->nodes.size(); ++i) {
-    const tk::Node& n = mod->nodes[i];
-    for (int k = 0; k < n.desc.n_outputs; ++k) {
-      char* h = (char*)dst[i * TK_MAX_NODE_OUTPUTS + k];
-      const int64_t nb = tk::nbytes(&n.out[k].t);
-      if (h && nb > 0) recs->push_back({h, tk::ptr(&n.out[k].t), nb, (int)i, k, &n.out[k].t, false, false, false});
-    }
-  }
-  std::sort(recs->begin(), recs->end(), [](const PackRecord& a, const PackRecord& b) { return a.host < b.host; });
-  for (size_t r = 0; r + 1 < recs->size(); ++r)
-    if ((*recs)[r].host + (*recs)[r].bytes > (*recs)[r + 1].host) {
-      tk::set_error("tk_module_run_graph: overlapping record destinations");
-      return TK_ERR_INVALID_ARG;
-    }
-  return TK_OK;
-}
-
-// the tensor that output k of node n clips, where the node declares that output as a clip
-static const void* clip_input(const tk::Node& n, int k) {
-  const tk_node& d = n.desc;
-  const bool block = d.kind == TK_NODE_CONV_BLOCK || d.kind == TK_NODE_DENSE_BLOCK;
-  if ((block && d.attrs.block.has_clip) || (d.kind == TK_NODE_ADD_BLOCK && d.attrs.add_block.has_clip))
-    return k >= 1 && k == d.n_outputs - 1 ? tk::ptr(&n.out[k - 1].t) : nullptr;
-  return d.kind == TK_NODE_CLIP && k == 0 ? tk::ptr(&n.in[0].t) : nullptr;
-}
-
-// The bias that output k of node n adds to the tensor at `from`, where the node declares that
-// output as the bias_add of that tensor: output 1 of a conv or dense block over its output 0, or a
-// TK_NODE_BIAS_ADD over its input.  *axis: the record's axis the bias runs along.
-static const tk_tensor* bias_input(const tk::Node& n, int k, const void* from, int* axis) {
-  const tk_node& d = n.desc;
-  if ((d.kind == TK_NODE_CONV_BLOCK || d.kind == TK_NODE_DENSE_BLOCK) && k == 1 && d.n_inputs >= 3 &&
-      tk::ptr(&n.out[0].t) == from) {
-    *axis = d.kind == TK_NODE_CONV_BLOCK ? 1 : n.out[1].t.ndim - 1;
-    return &n.in[2].t;
-  }
-  if (d.kind == TK_NODE_BIAS_ADD && k == 0 && d.n_inputs >= 2 && tk::ptr(&n.in[0].t) == from) {
-    *axis = d.attrs.bias_add.axis < 0 ? d.attrs.bias_add.axis + n.out[0].t.ndim : d.attrs.bias_add.axis;
-    return &n.in[1].t;
-  }
-  return nullptr;
-}
-
-// int32 records are coded; one that follows (in the image) a coded record of its own shape is
-// coded as the difference from it (every bias_add after its convolution), and where its node
-// declares it as the bias_add of that record, with a compact int32 bias of the axis' length and
-// fewer than 2^31 elements, as the difference less the bias (tk_wire.h: bias coding; the values are
-// a snapshot the plan takes, never the live tensor; TK_WIRE_BIAS=0 keeps plain differences).  A compact 1-byte
-// record that its node declares as the clip of the record before it in the image (same dtype
-// and shape) is coded as a clamp of that record; every other 1-byte record stays raw.  Returns
-// whether any record is coded.
-static bool decide_coding(const tk_module* mod, std::vector<PackRecord>& recs) {
-  bool any = false;
-  for (size_t r = 0; r < recs.size(); ++r) {
-    PackRecord& c = recs[r];
-    const tk_tensor* a = c.t;
-    const tk_tensor* b = r ? recs[r - 1].t : nullptr;
-    const bool same_shape = b && a->ndim == b->ndim && std::equal(a->shape, a->shape + a->ndim, b->shape);
-    if (mod->wire_clamp && tk::is_int8ish(a) && tk::compact(a) && same_shape && tk::compact(b) &&
-        a->dtype.code == b->dtype.code && b->dtype.bits == 8 && b->dtype.lanes == 1 && c.src != recs[r - 1].src &&
-        clip_input(mod->nodes[c.node], c.out) == recs[r - 1].src) {
-      c.wire = c.clamp = any = true;
-      continue;
-    }
-    c.wire = tk::is_int(c.t, 32) && tk::compact(c.t) && ((uintptr_t)c.src & 3) == 0;
-    any |= c.wire;
-    if (!c.wire || r == 0 || !recs[r - 1].wire) continue;
-    c.diff = same_shape && tk::is_int(b, 32) && c.src != recs[r - 1].src;
-    int axis = 0;
-    const tk_tensor* bias = c.diff && mod->wire_bias ? bias_input(mod->nodes[c.node], c.out, recs[r - 1].src, &axis) : nullptr;
-    if (!bias || !bias->data || axis < 0 || axis >= a->ndim || !tk::is_int(bias, 32) || !tk::compact(bias) ||
-        tk::numel(bias) != a->shape[axis] || a->shape[axis] < 1 || a->shape[axis] >= ((int64_t)1 << 31) ||
-        tk::numel(a) >= ((int64_t)1 << 31))
-      continue;
-    int64_t plane = 1;
-    for (int d = axis + 1; d < a->ndim; ++d) plane *= a->shape[d];
-    c.bias = bias, c.plane = (int32_t)plane, c.channels = (int32_t)a->shape[axis];
-  }
-  return any;
-}
-
-// A chunk's wire tables, planned by tk::wire_plan from its coded records (`coded`: their indices in
-// `recs`): the encoder's segments (record buffers on the device), the host decoder's (image bytes),
-// the decode units and the size of a slot with every block raw.
-static int chunk_wire_tables(const std::vector<PackRecord>& recs, const std::vector<size_t>& coded, const PackPlan* plan,
-                             PackPlan::WireChunk* wc, std::vector<tk::WireSegDev>& wire_segs) {
-  std::vector<tk_wire_record> wrecs;  // offsets are not used here
-  for (size_t q = 0; q < coded.size(); ++q) {
-    const PackRecord& r = recs[coded[q]];
-    // a record follows its predecessor in the decode order only where that one is coded in this
-    // chunk too (a difference, or a clamp of a clamp); an earlier chunk's record, or a raw
-    // predecessor, has landed by then
-    const bool chained = (r.diff || r.clamp) && q > 0 && coded[q - 1] == coded[q] - 1;
-    const int esize = tk::elem_bytes(r.t);
-    wrecs.push_back({0, r.bytes / esize, chained, esize == 4 ? tk::kWireI32 : tk::is_int(r.t, 8) ? tk::kWireI8 : tk::kWireU8});
-  }
-  tk::WirePlan wp;
-  if (const int rc = tk::wire_plan(wrecs.data(), (int)wrecs.size(), -1, "tk_module_run_graph", &wp)) return rc;
-  wc->units = std::move(wp.units);
-  wc->seg_off = (int64_t)wire_segs.size();
-  wc->bound = wp.bound;
-  for (const tk::WireSegRef& sr : wp.segs) {
-    const PackRecord& r = recs[coded[sr.rec]];
-    // a differenced record's predecessor is the record before it in the image (this chunk's
-    // or, for the chunk's first record, an earlier chunk's: decoded before this one)
-    const PackRecord* pv = r.diff || r.clamp ? &recs[coded[sr.rec] - 1] : nullptr;
-    const int kind = wrecs[sr.rec].kind;
-    const tk::WireSegAddr dev = tk::wire_seg_addr(sr, kind, r.src, pv ? pv->src : nullptr);
-    const tk::WireSegAddr img = tk::wire_seg_addr(sr, kind, r.host, pv ? pv->host : nullptr);
-    wire_segs.push_back({dev.at, dev.prev, sr.n, kind});
-    wc->segs.push_back({img.at, img.prev, sr.n, kind});
-    if (r.bias) {  // each side is handed its own copy of the plan's snapshot
-      tk::wire_seg_bias(&wire_segs.back(), plan->addend_dev + r.addend_at, r.plane, r.channels, sr.e0);
-      tk::wire_seg_bias(&wc->segs.back(), plan->addend_host.data() + r.addend_at, r.plane, r.channels, sr.e0);
-    }
-  }
-  for (size_t q : coded) wc->coded_bytes += recs[q].bytes;
-  return TK_OK;
-}
-
-// The plan's snapshot of the bias vectors its records are coded with (PackPlan::addend_dev /
-// addend_host): each vector copied device to device into one buffer, and that buffer to the host.
-static int snapshot_addends(PackPlan* plan, std::vector<PackRecord>& recs) {
-  int64_t total = 0;
-  for (PackRecord& r : recs)
-    if (r.bias) r.addend_at = total, total += r.channels;
-  if (!total) return TK_OK;
-  TK_HIP(hipMalloc((void**)&plan->addend_dev, (size_t)total * sizeof(int32_t)));
-  for (const PackRecord& r : recs)
-    if (r.bias)
-      TK_HIP(hipMemcpy(plan->addend_dev + r.addend_at, tk::ptr(r.bias), (size_t)r.channels * sizeof(int32_t),
-                       hipMemcpyDeviceToDevice));
-  plan->addend_host.resize((size_t)total);
-  TK_HIP(hipMemcpy(plan->addend_host.data(), plan->addend_dev, (size_t)total * sizeof(int32_t), hipMemcpyDeviceToHost));
-  return TK_OK;
-}
-
-// The chunks, cut at node boundaries where every record below the cut is written, with the pack
-// table and, on the wire, each chunk's raw ranges and wire tables.
-static int cut_chunks(const tk_module* mod, const std::vector<PackRecord>& recs, PackPlan* plan,
-                      std::vector<PackRecHost>& table, std::vector<tk::WireSegDev>& wire_segs) {
-  // after node i, every record below complete_upto[i] (host order) is written
-  const int nn = (int)mod->nodes.size();
-  std::vector<int64_t> complete_upto(nn);
-  std::vector<int> prefix_max(recs.size());  // max producer node among records [0, q]
-  for (size_t q = 0; q < recs.size(); ++q) prefix_max[q] = std::max(q ? prefix_max[q - 1] : -1, recs[q].node);
-  for (int i = 0, r = 0; i < nn; ++i) {
-    while (r < (int)recs.size() && prefix_max[r] <= i) ++r;
-    complete_upto[i] = r == (int)recs.size() ? plan->span : recs[r].host - plan->host_lo;
-  }
-  const int64_t target = std::max<int64_t>(1, (plan->span + mod->pack_chunks - 1) / mod->pack_chunks);
-  int64_t cut = 0;
-  size_t next_rec = 0;
-  for (int i = 0; i < nn; ++i) {
-    const int64_t upto = complete_upto[i];
-    if (upto <= cut) continue;
-    if (upto - cut < target && upto < plan->span) continue;
-    PackPlan::Chunk c{i, cut, upto - cut, (int64_t)table.size(), 0, 0};
-    int64_t blocks = 0;
-    PackPlan::WireChunk wc;
-    std::vector<size_t> w_rec;  // the chunk's coded records
-    bool in_run = false;  // the previous record of this chunk was not coded
-    while (next_rec < recs.size() && recs[next_rec].host - plan->host_lo < upto) {
-      const PackRecord& rc = recs[next_rec++];
-      const int64_t off = rc.host - plan->host_lo;
-      if (rc.wire) {
-        w_rec.push_back(next_rec - 1);
-        in_run = false;
-        continue;
-      }
-      if (plan->wire) {
-        if (in_run) wc.raw.back().len = off + rc.bytes - wc.raw.back().off;
-        else wc.raw.push_back({off, rc.bytes});
-        in_run = true;
-      }
-      const int64_t a0 = off & ~(int64_t)15;
-      const int64_t nblk = (off + rc.bytes - a0 + 256 * 16 - 1) / (256 * 16);
-      table.push_back({rc.src, off, rc.bytes, blocks});
-      blocks += nblk;
-      ++c.n_rec;
-    }
-    c.blocks = blocks;
-    plan->chunks.push_back(c);
-    cut = upto;
-    if (!plan->wire) continue;
-    if (!w_rec.empty())
-      if (const int rc = chunk_wire_tables(recs, w_rec, plan, &wc, wire_segs)) return rc;
-    plan->wchunks.push_back(std::move(wc));
-  }
-  if (cut != plan->span || next_rec != recs.size()) {
-    tk::set_error("tk_module_run_graph: pack plan does not cover every record");
-    return TK_ERR_INVALID_ARG;
-  }
-  return TK_OK;
-}
-
-// The device pack table, two mirrors and their events; on the wire also the device segment table,
-// a ring of pinned slots each large enough for any chunk with every block raw, a cursor per slot,
-// the decode calls of every (chunk, slot) pair and the module's streams.
-static int alloc_pack_resources(tk_module* mod, PackPlan* plan, const std::vector<PackRecHost>& table,
-                                const std::vector<tk::WireSegDev>& wire_segs) {
-  if (!table.empty()) {
-    TK_HIP(hipMalloc(&plan->table, table.size() * sizeof(PackRecHost)));
-    TK_HIP(hipMemcpy(plan->table, table.data(), table.size() * sizeof(PackRecHost), hipMemcpyHostToDevice));
-  }
-  if (plan->wire) {
-    TK_HIP(hipMalloc(&plan->wire_segs, wire_segs.size() * sizeof(tk::WireSegDev)));
-    TK_HIP(hipMemcpy(plan->wire_segs, wire_segs.data(), wire_segs.size() * sizeof(tk::WireSegDev), hipMemcpyHostToDevice));
-    int64_t slot_bytes = 0;
-    int coded_chunks = 0;
-    for (const auto& w : plan->wchunks) slot_bytes = std::max(slot_bytes, w.bound), coded_chunks += !w.segs.empty();
-    const int n_slots = std::min(3, coded_chunks);
-    for (int k = 0; k < n_slots; ++k) {
-      void* p = nullptr;
-      TK_HIP(hipHostMalloc(&p, (size_t)slot_bytes, hipHostMallocDefault));
-      plan->slots.push_back(p);
-      hipEvent_t e;
-      TK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      plan->slot_done.push_back(e);
-    }
-    plan->slot_used.assign(n_slots, 0);
-    TK_HIP(hipMalloc((void**)&plan->cursors, n_slots * sizeof(uint32_t)));
-    for (auto& w : plan->wchunks) {
-      if (w.segs.empty()) continue;
-      TK_HIP(hipEventCreateWithFlags(&w.landed, hipEventDisableTiming));
-      w.calls.reset(new PackPlan::WireCall[n_slots]);
-      for (int k = 0; k < n_slots; ++k) {
-        tk::WireJob& j = w.calls[k].job;
-        j.wire = (const char*)plan->slots[k];
-        j.wire_bytes = w.bound;
-        j.segs = w.segs.data(), j.n_seg = (int64_t)w.segs.size();
-        j.units = w.units.data(), j.n_units = (int64_t)w.units.size();
-        w.calls[k].failed = &mod->wire_failed;
-      }
-    }
-    if (!mod->wire_s) TK_HIP(hipStreamCreateWithFlags(&mod->wire_s, hipStreamNonBlocking));
-    if (!mod->dec_s) TK_HIP(hipStreamCreateWithFlags(&mod->dec_s, hipStreamNonBlocking));
-    if (!mod->wire_tail) TK_HIP(hipEventCreateWithFlags(&mod->wire_tail, hipEventDisableTiming));
-    if (!mod->decode_tail) TK_HIP(hipEventCreateWithFlags(&mod->decode_tail, hipEventDisableTiming));
-  }
-  for (int m = 0; m < 2; ++m) {
-    // the mirror holds the image's bytes between records (headers) from the start
-    TK_HIP(hipMalloc(&plan->mirror[m], (size_t)plan->span + 16));
-    TK_HIP(hipMemcpy(plan->mirror[m], plan->host_lo, (size_t)plan->span, hipMemcpyHostToDevice));
-    TK_HIP(hipEventCreateWithFlags(&plan->mirror_done[m], hipEventDisableTiming));
-    plan->ev[m].resize(plan->chunks.size(), nullptr);
-    for (auto& e : plan->ev[m]) TK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  }
-  if (!mod->cap_s) TK_HIP(hipStreamCreateWithFlags(&mod->cap_s, hipStreamNonBlocking));
-  return TK_OK;
-}
-
-// One graph per chunk and mirror: the nodes up to the chunk's last producer and its pack kernel (a
-// tail graph holds the nodes after the last chunk).  The copy of chunk c waits on an event recorded
-// between graph launches c and c + 1; external event-record nodes inside one graph would do the
-// same in one launch, but torch's bundled HIP runtime (7.0) refuses them in capture.
-static int capture_chunk_graphs(tk_module* mod, PackPlan* plan) {
-  const int nn = (int)mod->nodes.size();
-  const int nseg = (int)plan->chunks.size() + (plan->chunks.back().after_node < nn - 1 ? 1 : 0);
-  for (int m = 0; m < 2; ++m) {
-    hipStream_t qs = mod->cap_s;
-    int i = 0;
-    for (int seg = 0; seg < nseg; ++seg) {
-      const bool has_chunk = seg < (int)plan->chunks.size();
-      const int last = has_chunk ? plan->chunks[seg].after_node : nn - 1;
-      TK_HIP(hipStreamBeginCapture(qs, hipStreamCaptureModeThreadLocal));
-      int rc = TK_OK;
-      for (; i <= last && rc == TK_OK; ++i) {
-        rc = tk::run_node(mod->nodes[i], qs);
-        if (rc) tk::set_error("node " + std::to_string(i) + ": " + tk_last_error());
-      }
-      if (rc == TK_OK && has_chunk && plan->chunks[seg].n_rec > 0) {
-        const PackPlan::Chunk& ch = plan->chunks[seg];
-        rc = tk::pack_records_impl((const char*)plan->table + ch.table_off * sizeof(PackRecHost), ch.n_rec, ch.blocks,
-                                   plan->mirror[m], qs);
-      }
-      hipGraph_t g = nullptr;
-      hipError_t e = hipStreamEndCapture(qs, &g);
-      if (rc) {
-        if (g) (void)hipGraphDestroy(g);
-        return rc;
-      }
-      if (e != hipSuccess || !g) {
-        (void)hipGetLastError();
-        tk::set_error(std::string("tk_module_run_graph: stream capture failed: ") + hipGetErrorString(e));
-        return TK_ERR_HIP;
-      }
-      plan->g[m].push_back(g);
-      hipGraphExec_t ge = nullptr;
-      e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
-      if (e != hipSuccess) {
-        tk::set_error(std::string("tk_module_run_graph: instantiate failed: ") + hipGetErrorString(e));
-        return TK_ERR_HIP;
-      }
-      plan->ge[m].push_back(ge);
-    }
-  }
-  return TK_OK;
-}
-
-// Builds the packed-capture plan for host destinations `dst`: the mirrored range, the chunks (cut
-// at node boundaries where every record below the cut is written), the device pack tables, two
-// mirrors loaded with the host image's bytes, and one graph per chunk and mirror.
-static int build_pack_plan(tk_module* mod, const std::vector<void*>& dst, PackPlan** out) {
-  auto plan = std::make_unique<PackPlan>();
-  plan->dst = dst;
-  std::vector<PackRecord> recs;
-  if (const int rc = collect_records(mod, dst, &recs)) return rc;
-  if (recs.empty()) {
-    *out = nullptr;
-    return TK_OK;
-  }
-  plan->wire = mod->trace_wire && !mod->wire_forced_off && decide_coding(mod, recs);
-  plan->host_lo = recs.front().host;
-  plan->span = recs.back().host + recs.back().bytes - plan->host_lo;
-  std::vector<PackRecHost> table;
-  std::vector<tk::WireSegDev> wire_segs;
-  if (plan->wire)
-    if (const int rc = snapshot_addends(plan.get(), recs)) return rc;
-  if (const int rc = cut_chunks(mod, recs, plan.get(), table, wire_segs)) return rc;
-  if (const int rc = alloc_pack_resources(mod, plan.get(), table, wire_segs)) return rc;
-  if (const int rc = capture_chunk_graphs(mod, plan.get())) return rc;
-  *out = plan.release();
-  return TK_OK;
-}
-
-// The decode host function of one chunk (decode stream): widens the chunk's slot into the image
-// on the decoder's pool and waits for it; no HIP call.
-static void wire_decode_call(void* p) {
-  auto* call = static_cast<PackPlan::WireCall*>(p);
-  if (tk::wire_decode(&call->job, 0)) call->failed->store(1);
-}
-
-// The wire side of one chunk of a packed run, after the chunk's graph and its event on s:
-//   s       graph c | ev ................ graph c+1 | ev ...
-//   wire_s  wait ev, wait slot_done[k] | cursor = 0 | encode -> slot k | raw copies | landed[c]
-//   dec_s   wait landed[c] | host function: decode slot k -> image | slot_done[k]
-static int enqueue_wire_chunk(tk_module* mod, PackPlan* plan, int m, size_t c, bool trace) {
-  const PackPlan::Chunk& ch = plan->chunks[c];
-  PackPlan::WireChunk& w = plan->wchunks[c];
-  hipStream_t ws = mod->wire_s, ds = mod->dec_s;
-  TK_HIP(hipStreamWaitEvent(ws, plan->ev[m][c], 0));
-  if (trace) TK_HIP(hipEventRecord(mod->ct_ev[2 * c], ws));
-  int k = -1;
-  if (!w.segs.empty()) {
-    k = plan->slot_next;
-    plan->slot_next = (k + 1) % (int)plan->slots.size();
-    if (plan->slot_used[k]) TK_HIP(hipStreamWaitEvent(ws, plan->slot_done[k], 0));
-    TK_HIP(hipMemsetAsync(plan->cursors + k, 0, sizeof(uint32_t), ws));
-    const int rc = tk::wire_encode_impl((const tk::WireSegDev*)plan->wire_segs + w.seg_off, (int64_t)w.segs.size(),
-                                        plan->cursors + k, plan->slots[k], w.bound, ws);
-    if (rc) return rc;
-  }
-  for (const PackPlan::Range& r : w.raw)
-    TK_HIP(hipMemcpyAsync(plan->host_lo + r.off, (char*)plan->mirror[m] + r.off, (size_t)r.len, hipMemcpyDeviceToHost, ws));
-  if (trace) {
-    TK_HIP(hipEventRecord(mod->ct_ev[2 * c + 1], ws));
-    mod->ct_bytes[c] = ch.len;
-  }
-  if (k >= 0) {
-    TK_HIP(hipEventRecord(w.landed, ws));
-    TK_HIP(hipStreamWaitEvent(ds, w.landed, 0));
-    TK_HIP(hipLaunchHostFunc(ds, wire_decode_call, &w.calls[k]));
-    TK_HIP(hipEventRecord(plan->slot_done[k], ds));
-    plan->slot_used[k] = 1;
-    w.last_slot = k;
-  }
-  return TK_OK;
-}
-
-// One packed traced run: the chunk graphs of mirror m (kernels, pack kernel) on s, each followed by
-// an event, and the chunk copies on cs, each after its event (wire runs: enqueue_wire_chunk).
-static int run_packed(tk_module* mod, hipStream_t s, hipStream_t cs, void* const* host_dst) {
-  const size_t nd = mod->nodes.size() * TK_MAX_NODE_OUTPUTS;
-  std::vector<void*> dst(host_dst, host_dst + nd);
-  PackPlan* plan = nullptr;
-  for (auto& p : mod->packs)
-    if (p->dst == dst) plan = p.get();
-  if (!plan) {
-    if (mod->packs.size() >= 2) {  // keep the newest (a file sink alternates two images)
-      TK_HIP(hipDeviceSynchronize());
-      if (mod->last_wire_plan == mod->packs.front().get()) mod->last_wire_plan = nullptr;
-      mod->packs.erase(mod->packs.begin());
-    }
-    PackPlan* built = nullptr;
-    int rc = build_pack_plan(mod, dst, &built);
-    if (rc) return rc;
-    if (!built) return tk::TK_OK_RUN;  // nothing to capture
-    mod->packs.emplace_back(built);
-    plan = built;
-  }
-  // a previous per-record (unpacked) capture still reads the record buffers on cs
-  if (mod->capture_recorded && mod->capture_plain) TK_HIP(hipStreamWaitEvent(s, mod->capture_done, 0));
-  const int m = plan->next;
-  plan->next ^= 1;
-  // the pack into mirror m waits for that mirror's last copies (two runs ago); the records the
-  // kernels overwrite are only read by the packs of the previous launch on the same stream
-  if (plan->mirror_used[m]) TK_HIP(hipStreamWaitEvent(s, plan->mirror_done[m], 0));
-  if (mod->wire_failed.load()) {
-    tk::set_error("tk_module_run_graph: a wire buffer of an earlier run did not decode");
-    return TK_ERR_INVALID_ARG;
-  }
-  // the encode kernels of the last wire run read the record buffers this run overwrites
-  if (mod->wire_tail_used) TK_HIP(hipStreamWaitEvent(s, mod->wire_tail, 0));
-  const bool trace = mod->copy_trace;
-  if (trace) {
-    if (!mod->ct_t0) TK_HIP(hipEventCreate(&mod->ct_t0));
-    while (mod->ct_ev.size() < 2 * plan->chunks.size()) {
-      hipEvent_t e;
-      TK_HIP(hipEventCreate(&e));
-      mod->ct_ev.push_back(e);
-    }
-    mod->ct_bytes.assign(plan->chunks.size(), 0);
-    TK_HIP(hipEventRecord(mod->ct_t0, s));
-  }
-  for (size_t c = 0; c < plan->ge[m].size(); ++c) {
-    TK_HIP(hipGraphLaunch(plan->ge[m][c], s));
-    if (c >= plan->chunks.size()) break;  // the tail graph
-    const PackPlan::Chunk& ch = plan->chunks[c];
-    TK_HIP(hipEventRecord(plan->ev[m][c], s));
-    if (plan->wire) {
-      const int rc = enqueue_wire_chunk(mod, plan, m, c, trace);
-      if (rc) return rc;
-      continue;
-    }
-    TK_HIP(hipStreamWaitEvent(cs, plan->ev[m][c], 0));
-    if (trace) TK_HIP(hipEventRecord(mod->ct_ev[2 * c], cs));
-    TK_HIP(hipMemcpyAsync(plan->host_lo + ch.off, (char*)plan->mirror[m] + ch.off, (size_t)ch.len,
-                          hipMemcpyDeviceToHost, cs));
-    if (trace) {
-      TK_HIP(hipEventRecord(mod->ct_ev[2 * c + 1], cs));
-      mod->ct_bytes[c] = ch.len;
-    }
-  }
-  if (plan->wire) {
-    // the capture stream waits for the run's last wire work and last decode, so that capture_done
-    // (and the capture stream's synchronisation) still means "the image is complete"
-    TK_HIP(hipEventRecord(mod->wire_tail, mod->wire_s));
-    TK_HIP(hipEventRecord(plan->mirror_done[m], mod->wire_s));
-    TK_HIP(hipEventRecord(mod->decode_tail, mod->dec_s));
-    mod->wire_tail_used = true;
-    mod->last_wire_plan = plan;
-    TK_HIP(hipStreamWaitEvent(cs, mod->wire_tail, 0));
-    TK_HIP(hipStreamWaitEvent(cs, mod->decode_tail, 0));
-  } else {
-    TK_HIP(hipEventRecord(plan->mirror_done[m], cs));
-    mod->last_wire_plan = nullptr;
-  }
-  plan->mirror_used[m] = true;
-  TK_HIP(hipEventRecord(mod->capture_done, cs));
-  mod->capture_recorded = true;
-  mod->capture_plain = false;
-  return TK_OK;
-}
-
-int tk_module_set_copy_trace(tk_module* mod, int enable) {
-  if (!mod) {
-    tk::set_error("tk_module_set_copy_trace: null module");
-    return TK_ERR_INVALID_ARG;
-  }
-  mod->copy_trace = enable != 0;
-  mod->ct_bytes.clear();
-  return TK_OK;
-}
-
-int tk_module_set_trace_wire(tk_module* mod, int enable) {
-  if (!mod || (enable != 0 && enable != 1)) {
-    tk::set_error("tk_module_set_trace_wire: invalid argument");
-    return TK_ERR_INVALID_ARG;
-  }
-  if (mod->trace_wire != (enable != 0)) mod->drop_graph();
-  mod->trace_wire = enable != 0;
-  return TK_OK;
-}
-
-int tk_module_wire_stats(tk_module* mod, double* out, int max_chunks) {
-  if (!mod || (max_chunks > 0 && !out)) {
-    tk::set_error("tk_module_wire_stats: invalid argument");
-    return TK_ERR_INVALID_ARG;
-  }
-  PackPlan* plan = mod->last_wire_plan;
-  if (!plan) return 0;
-  TK_HIP(hipEventSynchronize(mod->decode_tail));
-  if (mod->wire_failed.load()) {
-    tk::set_error("tk_module_wire_stats: a wire buffer did not decode");
-    return TK_ERR_INVALID_ARG;
-  }
-  const int n = (int)plan->wchunks.size();
-  for (int c = 0; c < n && c < max_chunks; ++c) {
-    const PackPlan::WireChunk& w = plan->wchunks[c];
-    const tk::WireJob* j = w.last_slot >= 0 ? &w.calls[w.last_slot].job : nullptr;
-    int64_t raw = 0;
-    for (const PackPlan::Range& r : w.raw) raw += r.len;
-    out[3 * c] = (double)((j ? j->used_bytes : 0) + raw);
-    out[3 * c + 1] = (double)w.coded_bytes;
-    out[3 * c + 2] = j ? j->ms : 0.0;
-  }
-  return n;
-}
-
-int tk_module_copy_trace(tk_module* mod, double* out, int max_chunks) {
-  if (!mod || (max_chunks > 0 && !out)) {
-    tk::set_error("tk_module_copy_trace: invalid argument");
-    return TK_ERR_INVALID_ARG;
-  }
-  const int n = (int)mod->ct_bytes.size();
-  for (int c = 0; c < n && c < max_chunks; ++c) {
-    float a = 0.f, b = 0.f;
-    TK_HIP(hipEventSynchronize(mod->ct_ev[2 * c + 1]));
-    TK_HIP(hipEventElapsedTime(&a, mod->ct_t0, mod->ct_ev[2 * c]));
-    TK_HIP(hipEventElapsedTime(&b, mod->ct_t0, mod->ct_ev[2 * c + 1]));
-    out[3 * c] = (double)mod->ct_bytes[c];
-    out[3 * c + 1] = a;
-    out[3 * c + 2] = b;
-  }
-  return n;
-}
-
 int tk_module_run_graph(tk_module* mod, void* stream, void* capture_stream, void* const* host_dst) {
   if (!mod) {
     tk::set_error("tk_module_run_graph: null module");
@@ -1286,7 +464,7 @@ int tk_module_run_graph(tk_module* mod, void* stream, void* capture_stream, void
   hipStream_t cs = tk::as_stream(capture_stream);
   const bool capture = capture_stream && host_dst;
   if (capture && mod->graph_packed) {
-    const int rc = run_packed(mod, s, cs, host_dst);
+    const int rc = tk::run_packed(mod, s, cs, host_dst);
     if (rc != tk::TK_OK_RUN) {
       mod->have_times = false;
       return rc;
@@ -1299,23 +477,18 @@ int tk_module_run_graph(tk_module* mod, void* stream, void* capture_stream, void
   int gi = -1;
   for (size_t i = 0; i < mod->graphs.size(); ++i)
     if (mod->graphs[i].dst == dst && (mod->graphs[i].cs != nullptr) == capture) gi = (int)i;
-  int rc0 = wait_capture(mod, s);
+  int rc0 = tk::wait_capture(mod, s);
   if (rc0) return rc0;
   if (gi < 0) {
-    if (mod->graphs.size() >= 4) {  // keep the newest few
-      tk_module::Graph& old = mod->graphs.front();
-      if (old.ge) (void)hipGraphExecDestroy(old.ge);
-      if (old.g) (void)hipGraphDestroy(old.g);
-      mod->graphs.erase(mod->graphs.begin());
-    }
-    if (!mod->graph_join) TK_HIP(hipEventCreateWithFlags(&mod->graph_join, hipEventDisableTiming));
-    if (!mod->cap_s) TK_HIP(hipStreamCreateWithFlags(&mod->cap_s, hipStreamNonBlocking));
-    if (!mod->cap_cs) TK_HIP(hipStreamCreateWithFlags(&mod->cap_cs, hipStreamNonBlocking));
+    if (mod->graphs.size() >= 4) mod->graphs.erase(mod->graphs.begin());  // keep the newest few
+    if (!mod->graph_join) TK_HIP(hipEventCreateWithFlags(mod->graph_join.put(), hipEventDisableTiming));
+    if (!mod->cap_s) TK_HIP(hipStreamCreateWithFlags(mod->cap_s.put(), hipStreamNonBlocking));
+    if (!mod->cap_cs) TK_HIP(hipStreamCreateWithFlags(mod->cap_cs.put(), hipStreamNonBlocking));
     hipStream_t qs = mod->cap_s, qcs = mod->cap_cs;
     hipStream_t chains[4] = {qcs, nullptr, nullptr, nullptr};
     const int nch = capture ? mod->graph_copy_chains : 1;
     for (int c = 1; c < nch; ++c) {
-      if (!mod->cap_cx[c - 1]) TK_HIP(hipStreamCreateWithFlags(&mod->cap_cx[c - 1], hipStreamNonBlocking));
+      if (!mod->cap_cx[c - 1]) TK_HIP(hipStreamCreateWithFlags(mod->cap_cx[c - 1].put(), hipStreamNonBlocking));
       chains[c] = mod->cap_cx[c - 1];
     }
     // capture: the node loop on qs, the copies forked onto qcs through the per-node events and
@@ -1333,27 +506,19 @@ int tk_module_run_graph(tk_module* mod, void* stream, void* capture_stream, void
         rc = TK_ERR_HIP;
       }
     }
-    hipGraph_t g = nullptr;
-    hipError_t e = hipStreamEndCapture(qs, &g);
-    if (rc) {
-      if (g) (void)hipGraphDestroy(g);
-      return rc;
-    }
-    if (e != hipSuccess || !g) {
+    tk::RunGraph x;
+    hipError_t e = hipStreamEndCapture(qs, x.g.put());
+    if (rc) return rc;
+    if (e != hipSuccess || !x.g) {
       (void)hipGetLastError();
       tk::set_error(std::string("tk_module_run_graph: stream capture failed: ") + hipGetErrorString(e));
       return TK_ERR_HIP;
     }
-    hipGraphExec_t ge = nullptr;
-    e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
+    e = hipGraphInstantiate(x.ge.put(), x.g, nullptr, nullptr, 0);
     if (e != hipSuccess) {
-      (void)hipGraphDestroy(g);
       tk::set_error(std::string("tk_module_run_graph: instantiate failed: ") + hipGetErrorString(e));
       return TK_ERR_HIP;
     }
-    tk_module::Graph x;
-    x.g = g;
-    x.ge = ge;
     x.s = qs;
     x.cs = capture ? qcs : nullptr;
     x.dst = std::move(dst);
@@ -1363,7 +528,7 @@ int tk_module_run_graph(tk_module* mod, void* stream, void* capture_stream, void
   if (capture) {
     // whatever the caller queued on the capture stream before this run (the graph-input copies)
     // completes before the launch, so that capture_done covers it as in tk_module_run
-    if (!mod->graph_pre) TK_HIP(hipEventCreateWithFlags(&mod->graph_pre, hipEventDisableTiming));
+    if (!mod->graph_pre) TK_HIP(hipEventCreateWithFlags(mod->graph_pre.put(), hipEventDisableTiming));
     TK_HIP(hipEventRecord(mod->graph_pre, cs));
     TK_HIP(hipStreamWaitEvent(s, mod->graph_pre, 0));
   }
@@ -1386,7 +551,7 @@ int tk_module_wait_capture(tk_module* mod, void* stream) {
     tk::set_error("tk_module_wait_capture: null module");
     return TK_ERR_INVALID_ARG;
   }
-  return wait_capture(mod, tk::as_stream(stream));
+  return tk::wait_capture(mod, tk::as_stream(stream));
 }
 
 int tk_module_run_range(tk_module* mod, int begin, int end, void* stream) {
@@ -1395,7 +560,7 @@ int tk_module_run_range(tk_module* mod, int begin, int end, void* stream) {
     return TK_ERR_INVALID_ARG;
   }
   hipStream_t s = tk::as_stream(stream);
-  int rc0 = wait_capture(mod, s);
+  int rc0 = tk::wait_capture(mod, s);
   if (rc0) return rc0;
   for (int i = begin; i < end; ++i) {
     int rc = tk::run_node(mod->nodes[i], s);
@@ -1415,7 +580,7 @@ int tk_module_run_order(tk_module* mod, const int32_t* order, int n, void* strea
       return TK_ERR_INVALID_ARG;
     }
   hipStream_t s = tk::as_stream(stream);
-  int rc0 = wait_capture(mod, s);
+  int rc0 = tk::wait_capture(mod, s);
   if (rc0) return rc0;
   for (int k = 0; k < n; ++k) {
     int rc = tk::run_node(mod->nodes[order[k]], s);
@@ -1457,8 +622,8 @@ static int build_chains(tk_module* mod, hipStream_t s) {
   }
   if (!table.empty()) {
     const int64_t table_bytes = tk::wire_align((int64_t)(table.size() * sizeof(tk::ChainDev)), 64);
-    TK_HIP(hipMalloc(&c.dev, (size_t)(table_bytes + n_report * (int64_t)sizeof(tk_wire_mismatch))));
-    c.report = (tk_wire_mismatch*)((char*)c.dev + table_bytes);
+    TK_HIP(hipMalloc(c.dev.put(), (size_t)(table_bytes + n_report * (int64_t)sizeof(tk_wire_mismatch))));
+    c.report = (tk_wire_mismatch*)((char*)c.dev.h + table_bytes);
     // once per module: wait, so that the table is there whichever stream a later call uses
     TK_HIP(hipMemcpyAsync(c.dev, table.data(), table.size() * sizeof(tk::ChainDev), hipMemcpyHostToDevice, s));
     TK_HIP(hipStreamSynchronize(s));
@@ -1499,7 +664,7 @@ int tk_module_check_chains(tk_module* mod, tk_wire_mismatch* report, int capacit
   }
   for (int k = 0; k < n; ++k) report[k].mismatches = 0, report[k].first = ~(uint64_t)0;
   if (c.n_chains == 0) return n;
-  if (const int rc = tk::chain_check_impl((const tk::ChainDev*)c.dev, c.n_chains, c.blocks, c.report, n, s)) return rc;
+  if (const int rc = tk::chain_check_impl((const tk::ChainDev*)c.dev.h, c.n_chains, c.blocks, c.report, n, s)) return rc;
   TK_HIP(hipMemcpyAsync(report, c.report, (size_t)n * sizeof(tk_wire_mismatch), hipMemcpyDeviceToHost, s));
   // the report is filled once the call's own work on `stream` is complete, as tk_compare_device_batch's
   if (hipStreamSynchronize(s) != hipSuccess) {
@@ -1518,7 +683,7 @@ int tk_module_run_profiled(tk_module* mod, void* stream, float* node_ms) {
   int rc0 = ensure_prof_events(mod);
   if (rc0) return rc0;
   hipStream_t s = tk::as_stream(stream);
-  rc0 = wait_capture(mod, s);
+  rc0 = tk::wait_capture(mod, s);
   if (rc0) return rc0;
   TK_HIP(hipEventRecord(mod->prof[0], s));
   for (size_t i = 0; i < n; ++i) {
@@ -1590,12 +755,11 @@ int tk_module_tune(tk_module* mod, void* stream, int max_candidates, int reps, i
     for (size_t i = 0; i < n * W; ++i) algo_out[i] = -1;
   if (us_out)
     for (size_t i = 0; i < n * W; ++i) us_out[i] = -1.0f;
-  int rc0 = wait_capture(mod, s);
+  int rc0 = tk::wait_capture(mod, s);
   if (rc0) return rc0;
-  hipEvent_t e0, e1;
-  TK_HIP(hipEventCreate(&e0));
-  if (hipEventCreate(&e1) != hipSuccess) {
-    (void)hipEventDestroy(e0);
+  tk::OwnedEvent e0, e1;
+  TK_HIP(hipEventCreate(e0.put()));
+  if (hipEventCreate(e1.put()) != hipSuccess) {
     tk::set_error("tk_module_tune: hipEventCreate failed");
     return TK_ERR_HIP;
   }
@@ -1614,7 +778,7 @@ int tk_module_tune(tk_module* mod, void* stream, int max_candidates, int reps, i
   // If the device cannot spare the flush buffer (a module near the memory limit: packed mirrors
   // are up to 4 x 7.45 GB at batch 64), the buffer shrinks to a quarter of the free memory, and
   // below 64 MiB the node is timed warm, back to back like the others, instead of failing the tune.
-  void* flush = nullptr;
+  tk::OwnedDev<void> flush;
   size_t flush_bytes = (size_t)512 << 20;
   bool flush_unavailable = false;
   auto timed_warm = [&](tk::Node& node, float* us) -> int {
@@ -1631,20 +795,20 @@ int tk_module_tune(tk_module* mod, void* stream, int max_candidates, int reps, i
     return TK_OK;
   };
   auto timed_cold = [&](tk::Node& node, float* us) -> int {
-    if (!flush && !flush_unavailable && hipMalloc(&flush, flush_bytes) != hipSuccess) {
-      flush = nullptr;
+    if (!flush && !flush_unavailable && hipMalloc(flush.put(), flush_bytes) != hipSuccess) {
+      flush.h = nullptr;
       (void)hipGetLastError();
       size_t free_b = 0, total_b = 0;
       if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b / 4 >= ((size_t)64 << 20)) {
         flush_bytes = (free_b / 4) & ~(((size_t)1 << 20) - 1);
-        if (hipMalloc(&flush, flush_bytes) != hipSuccess) {
-          flush = nullptr;
+        if (hipMalloc(flush.put(), flush_bytes) != hipSuccess) {
+          flush.h = nullptr;
           (void)hipGetLastError();
         }
       } else {
         (void)hipGetLastError();
       }
-      flush_unavailable = flush == nullptr;
+      flush_unavailable = !flush;
     }
     if (flush_unavailable) return timed_warm(node, us);
     float total = 0.0f;
@@ -1711,12 +875,7 @@ int tk_module_tune(tk_module* mod, void* stream, int max_candidates, int reps, i
       for (int c = 0; c < max_candidates; ++c) us_out[i * W + 1 + c] = r.us[c];
     }
   }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  if (flush) {
-    (void)hipStreamSynchronize(s);
-    (void)hipFree(flush);
-  }
+  if (flush) (void)hipStreamSynchronize(s);  // before the flush buffer is released
   return rc;
 }
 

@@ -1,17 +1,16 @@
 // The trace transport on the device, for gfx950: the kernels that carry trace records to host
 // memory and to trace files, and back for verification (record copy, trace image pack, wire encoder,
 // the packer's prefix sum, wire decoder, raw compare, digest), then the extern "C" entry points that
-// launch them on their own.  The packed capture (tk_runtime.cc) launches host_copy_impl,
-// pack_records_impl and wire_encode_impl; all else is file-local.  tk_wire.h has the wire format,
-// tk_wire.cc the planner and the host codec.
+// launch them on their own.  The packed capture (tk_capture.cc) launches pack_records_impl and
+// wire_encode_impl, the executor's graph copies host_copy_impl (tk_ops.h); all else is file-local.
+// tk_wire.h has the wire format, tk_wire.cc the planner and the host codec.
 #include <algorithm>
 #include <climits>
 #include <mutex>
 #include <string>
 #include <vector>
 
-#include "tk_common.h"
-#include "tk_wire.h"
+#include "tk_ops.h"
 
 namespace tk {
 
@@ -91,13 +90,7 @@ int host_copy_impl(const void* const* src, void* const* dst, const int64_t* byte
 // aligned chunk of the mirror: whole chunks from two aligned 16-byte source loads and a funnel
 // shift, partial chunks (next to a header) byte by byte, header bytes left as they are.  Record
 // buffers must be 16-byte aligned and readable in whole 16-byte chunks (torch allocations are).
-struct PackRec {
-  const uint8_t* src;
-  int64_t dst;        // offset in the mirror
-  int64_t bytes;
-  int64_t first_blk;  // first workgroup of this record in the launch
-};
-
+// PackRec, the table entry, and a record's workgroup count: tk_capture_plan.h.
 __device__ __forceinline__ uint32_t funnel(uint32_t lo, uint32_t hi, uint32_t r) {
   return r ? __builtin_amdgcn_alignbyte(hi, lo, r) : lo;
 }
@@ -147,10 +140,9 @@ __global__ __launch_bounds__(256) void pack_records_kernel(const PackRec* __rest
   }
 }
 
-int pack_records_impl(const void* table, int nrec, int64_t blocks, void* mirror, hipStream_t s) {
+int pack_records_impl(const PackRec* table, int nrec, int64_t blocks, void* mirror, hipStream_t s) {
   TK_CHECK_ARG(table && mirror && nrec > 0 && blocks > 0, "bad arguments");
-  hipLaunchKernelGGL(pack_records_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const PackRec*)table, nrec,
-                     (uint8_t*)mirror);
+  hipLaunchKernelGGL(pack_records_kernel, dim3((unsigned)blocks), dim3(256), 0, s, table, nrec, (uint8_t*)mirror);
   TK_LAUNCH_CHECK();
   return TK_OK;
 }

@@ -18,8 +18,9 @@
 #include <string>
 #include <thread>
 
+#include "tk_tensor.h"
+
 namespace tk {
-void set_error(const std::string& msg);
 
 int wire_plan(const tk_wire_record* recs, int n_recs, int64_t image_bytes, const char* who, WirePlan* p,
               const tk_wire_addend* addends, bool bias_ok) {

@@ -2,7 +2,7 @@
 // on the host; 1-byte records that are a clamp of the record before them leave as that statement
 // and are rebuilt on the host (tk_wire.cc: the planner, host decoder, thread pool and reference
 // encoder; tk_trace.hip: the device encoder, the device decoder that verifies and loads trace files
-// and their entry points; tk_runtime.cc: the packed capture that uses them).
+// and their entry points; tk_capture_plan.cc and tk_capture.cc: the packed capture that uses them).
 //
 // A record of n int32 elements is cut into blocks of kWireBlock elements and segments of
 // kWireSegBlocks blocks (the last block / segment of a record may be short).  The coded value of
