@@ -733,7 +733,11 @@ int tk_module_wire_stats(tk_module* mod, double* out, int max_chunks);
  * refused (TK_ERR_INVALID_ARG).  Every entry point that takes no addends -- tk_wire_encode_host,
  * tk_wire_decode, tk_wire_encode_device and, with them, the packed trace files' tk_wire_check,
  * tk_wire_pack_device and tk_wire_unpack_device (format version 2) -- refuses a record of kind 3
- * with TK_ERR_UNSUPPORTED.  tk_wire_bound: the worst-case wire size.  tk_wire_encode_host: the reference
+ * with TK_ERR_UNSUPPORTED.  Packed trace files of format version 3 carry the coding through
+ * tk_wire_check_bias, tk_wire_pack_device_bias and tk_wire_unpack_device_bias: the entry points of
+ * the same names with `addends` (device pointers for the two device ones; tk_wire_check_bias reads
+ * no addend value, so either will do), the same in everything else, and with null `addends` the
+ * entry points without.  tk_wire_bound: the worst-case wire size.  tk_wire_encode_host: the reference
  * encoder (reads the records from `image`), returns the wire bytes written.  tk_wire_decode:
  * widens `wire` into `image` on up to `threads` pool threads (<= 0: the pool, which is sized from
  * the CPU affinity mask, at most 16, TK_WIRE_THREADS overrides; tk_wire_threads reports it); a
@@ -781,6 +785,8 @@ int tk_wire_decode_bias(const tk_wire_record* recs, const tk_wire_addend* addend
                         int64_t wire_bytes, void* image, int64_t image_bytes, int threads);
 int tk_wire_encode_device_bias(const tk_wire_record* recs, const tk_wire_addend* addends, int n_recs,
                                const void* const* src, void* wire, int64_t wire_cap, void* stream);
+int64_t tk_wire_pack_device_bias(const tk_wire_record* recs, const tk_wire_addend* addends, int n_recs,
+                                 const void* const* src, void* wire, int64_t wire_cap, void* stream);
 
 /* The way back in: checking a wire buffer on the host, decoding it on the device.
  *
@@ -807,6 +813,13 @@ int tk_wire_encode_device_bias(const tk_wire_record* recs, const tk_wire_addend*
  * nothing read outside `wire` and the rest of that chain neither stored nor compared.
  * Synchronises `stream`.
  *
+ * tk_wire_check_bias / tk_wire_unpack_device_bias: the same for record lists with kind 3.  The
+ * check returns TK_OK exactly when tk_wire_decode_bias would accept the buffer and reads neither a
+ * payload byte nor an addend value.  The decoder reads addends[i].addend on the device; an element
+ * of a kind-3 record is prev + addend[(e / plane) % channels] + base + offset with int32
+ * wrap-around, the predecessor taken from registers as for a plain difference, and kinds 0 and 3
+ * chain with each other inside one decode unit.
+ *
  * tk_compare_device: n_elems elements of elem_bytes (1, 2, 4 or 8) bytes each in two device
  * buffers of any alignment, compared bit for bit; *report as above, the index counted in elements.
  * tk_compare_device_batch: n such pairs in one launch and one synchronisation, report[i] for pair
@@ -819,6 +832,11 @@ enum { TK_WIRE_UNPACK_STORE = 0, TK_WIRE_UNPACK_COMPARE = 1 };
 int tk_wire_check(const tk_wire_record* recs, int n_recs, const void* wire, int64_t wire_bytes);
 int tk_wire_unpack_device(const tk_wire_record* recs, int n_recs, const void* wire, int64_t wire_bytes,
                           void* const* dst, int mode, tk_wire_mismatch* report, void* stream);
+int tk_wire_check_bias(const tk_wire_record* recs, const tk_wire_addend* addends, int n_recs, const void* wire,
+                       int64_t wire_bytes);
+int tk_wire_unpack_device_bias(const tk_wire_record* recs, const tk_wire_addend* addends, int n_recs, const void* wire,
+                               int64_t wire_bytes, void* const* dst, int mode, tk_wire_mismatch* report,
+                               void* stream);
 int tk_compare_device(const void* expected, const void* got, int64_t n_elems, int elem_bytes,
                       tk_wire_mismatch* report, void* stream);
 int tk_compare_device_batch(const void* const* expected, const void* const* got, const int64_t* n_elems,
@@ -995,10 +1013,22 @@ int tk_ndlist_parse(const void* blob, int64_t blob_size, int cap, tk_array_meta*
  * before it has the same kind and shape; every other dtype is raw.  Readers follow the stored plan
  * and never recompute it.  tk_trace_layout / tk_trace_write_headers rebuild the version-1 layout
  * and headers from the json, the params and the plan's names / dtypes / shapes, tk_wire_decode
- * expands the coded records: unpacking gives the version-1 file byte for byte. */
+ * expands the coded records: unpacking gives the version-1 file byte for byte.
+ *
+ * Version 3, the packed file with bias coding (opt-in: pack_trace(bias=True),
+ * dump_trace(packed=True, bias=True)): as version 2, with the section header one field longer and
+ * an addends part in front of the wire:
+ *   u32 "TKPK" | u32 n_records | u64 plan_len | u64 wire_size | u64 raw_size | u64 addend_size |
+ *   plan | pad to 8 | addends | wire (tk_wire_encode_host_bias / tk_wire_pack_device_bias) | raw
+ * A plan entry with coding 3 (dtype int32, diff 1, fewer than 2^31 elements, after a coded int32
+ * entry of the same element count) is followed by u8 axis, u64 addend_off: its addend is the
+ * shape[axis] int32 values at byte addend_off (a multiple of 4) of the addends part, its plane the
+ * product of the dims behind `axis`.  The addends part is padded to 8.  The file is
+ * self-contained: readers take the addends from it, never from the graph or the params blob. */
 #define TK_TRACE_MAGIC 0x0045434152544B54ULL /* "TKTRACE\0" little-endian */
 #define TK_TRACE_VERSION 1
 #define TK_TRACE_VERSION_PACKED 2
+#define TK_TRACE_VERSION_PACKED_BIAS 3
 #define TK_TRACE_ALIGN 4096
 typedef struct {
   uint64_t magic, version, json_len, params_off, params_size, records_off, records_size;

@@ -475,6 +475,13 @@ SIGNATURES = {
     "tk_wire_check": (ctypes.c_int, [ctypes.POINTER(tk_wire_record), ctypes.c_int, _VP, _I64]),
     "tk_wire_unpack_device": (ctypes.c_int, [ctypes.POINTER(tk_wire_record), ctypes.c_int, _VP, _I64,
                                              ctypes.POINTER(_VP), ctypes.c_int, ctypes.POINTER(tk_wire_mismatch), _VP]),
+    "tk_wire_check_bias": (ctypes.c_int, [ctypes.POINTER(tk_wire_record), ctypes.POINTER(tk_wire_addend), ctypes.c_int,
+                                          _VP, _I64]),
+    "tk_wire_pack_device_bias": (_I64, [ctypes.POINTER(tk_wire_record), ctypes.POINTER(tk_wire_addend), ctypes.c_int,
+                                        ctypes.POINTER(_VP), _VP, _I64, _VP]),
+    "tk_wire_unpack_device_bias": (ctypes.c_int, [ctypes.POINTER(tk_wire_record), ctypes.POINTER(tk_wire_addend),
+                                                  ctypes.c_int, _VP, _I64, ctypes.POINTER(_VP), ctypes.c_int,
+                                                  ctypes.POINTER(tk_wire_mismatch), _VP]),
     "tk_compare_device": (ctypes.c_int, [_VP, _VP, _I64, ctypes.c_int, ctypes.POINTER(tk_wire_mismatch), _VP]),
     "tk_compare_device_batch": (ctypes.c_int, [ctypes.POINTER(_VP), ctypes.POINTER(_VP), ctypes.POINTER(_I64),
                                                ctypes.POINTER(ctypes.c_int32), ctypes.c_int,

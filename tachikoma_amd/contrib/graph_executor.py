@@ -121,18 +121,52 @@ class PackedCapture:
     moves both into the staging at their place in the file.  No trace image exists and the host
     decoder is not involved.  The staging is sized once from tk_wire_bound (head + worst-case wire +
     raw records), not grown on demand: the worst case is the records' own size plus 2 %, and a
-    buffer that never moves can be written from while the other one fills."""
+    buffer that never moves can be written from while the other one fills.
 
-    def __init__(self, module: DeviceModule, meta: Dict[str, Any]):
+    With ``bias`` the file is version 3: an int32 record that plan.ops declares the nn.bias_add
+    (axis 1) of the record directly before it, with an int32 param of shape[1] values as its bias
+    and fewer than 2^31 elements, is bias-coded; every other record keeps the version-2 rule.  The
+    capture owns one device int32 buffer with all addends (at the front of the wire buffer),
+    refreshed together with the params; the packer reads it (tk_wire_pack_device_bias) and the
+    bytes of that very buffer are copied into the file's addends part on the pack's stream, so the
+    encoder's values and the file's cannot differ."""
+
+    @staticmethod
+    def bias_records(plan) -> Dict[int, Tuple[int, str]]:
+        """{record index: (axis, bias param name)} of the records the bias rule selects."""
+        records = plan.records
+        rule = tf.plan_records([(t.name, t.shape, t.dtype) for t in records])
+        index = {t.name: i for i, t in enumerate(records)}
+        params = {t.name: t for t in plan.params}
+        out = {}
+        for o in plan.ops:
+            i = index[o.name]
+            if o.op != "nn.bias_add" or rule[i] != (0, 1) or len(o.inputs) != 2 or o.attrs.get("axis") != 1:
+                continue
+            b = params.get(o.inputs[1])
+            if (o.inputs[0] == records[i - 1].name and b is not None and b.dtype == "int32" and
+                    tf._n_elems(b.shape) == int(o.out.shape[1]) and tf._n_elems(o.out.shape) < 1 << 31):
+                out[i] = (1, b.name)
+        return out
+
+    def __init__(self, module: DeviceModule, meta: Dict[str, Any], bias: bool = False):
         import ctypes
         import torch
         self.module = module
         self.lib = module.lib
+        self.bias = bool(bias)
         plan = module.plan
         params = [(t.name, t.shape, t.dtype) for t in plan.params]
         records = [(t.name, t.shape, t.dtype) for t in plan.records]
         self.meta = dict(meta)
-        self.entries = tf.packed_entries(records)
+        chosen = self.bias_records(plan) if self.bias else {}
+        self.entries = tf.packed_entries(records, bias_axes={i: a for i, (a, _) in chosen.items()})
+        # bias param name -> [(first int32 of its addend in the addends part, values)]
+        self.addend_of: Dict[str, List[Tuple[int, int]]] = {}
+        for i, (_, name) in chosen.items():
+            self.addend_of.setdefault(name, []).append((self.entries[i].addend_off // 4, self.entries[i].channels))
+        self.addend_bytes = tf.addend_bytes(self.entries) if self.bias else 0
+        self.addend_room = (self.addend_bytes + 63) // 64 * 64  # on the device: the wire behind it is 64-byte aligned
         # header, json and params blob are those of the version-1 file (laid out without records)
         self.layout, self.records_off = tf.head_layout(tf.header_json(self.meta), params)
         coded = [e for e in self.entries if e.coding != tf.RAW]
@@ -145,9 +179,13 @@ class PackedCapture:
             self.bound = int(self.lib.tk_wire_bound(self.recs, self.n_coded))
             if self.bound < 0:
                 _lib.check(self.bound, "tk_wire_bound")
-        self.section_head = len(tf.packed_section_head(self.entries, 0))
-        self.wire_off = self.records_off + self.section_head
-        self.wire = torch.empty(max(64, self.bound + self.raw_bytes), dtype=torch.uint8, device=module.device)
+        self.section_head = len(tf.packed_section_head(self.entries, 0, self.addend_bytes if self.bias else None))
+        self.addend_off = self.records_off + self.section_head
+        self.wire_off = self.addend_off + self.addend_bytes
+        buf = torch.empty(self.addend_room + max(64, self.bound + self.raw_bytes), dtype=torch.uint8, device=module.device)
+        self.addends, self.wire = buf[:self.addend_room], buf[self.addend_room:]
+        self.addends.zero_()  # the addends part's pad to 8 goes into the file; the wire stays uninitialised
+        self.ads = tf._wire_addends(self.entries, self.addends.data_ptr()) if self.bias else None
         self.image = torch.empty(self.wire_off + self.bound + self.raw_bytes, dtype=torch.uint8, pin_memory=True)
         self.ptr = self.image.data_ptr()
         self.layout.write_headers(self.ptr, self.layout.total)
@@ -165,6 +203,13 @@ class PackedCapture:
             off, shape, dtype = self.param_offsets[name]
             nbytes = int(np.prod(shape, dtype=np.int64)) * np.dtype(dtype).itemsize
             self.image[off:off + nbytes].copy_(_as_bytes(self.module.buffers[name]))
+            for at, count in self.addend_of.get(name, ()):
+                self.addends[4 * at:4 * (at + count)].copy_(_as_bytes(self.module.buffers[name]))
+        if self.addend_of:
+            # the copies above are device to device on the current stream: wait for them, as the copies
+            # into the params blob have been waited for, so that a pack on any stream reads these values
+            import torch
+            torch.cuda.current_stream(self.module.device).synchronize()
 
     def update_meta(self, **kw) -> None:
         """As TraceCapture.update_meta: the json keeps the length it had when the capture was made."""
@@ -188,7 +233,13 @@ class PackedCapture:
         stream.synchronize()
         t0 = time.perf_counter()
         used = 0
-        if self.n_coded:
+        if self.n_coded and self.bias:
+            used = int(self.lib.tk_wire_pack_device_bias(self.recs, self.ads, self.n_coded, self.src,
+                                                         ctypes.c_void_p(self.wire.data_ptr()), self.bound,
+                                                         ctypes.c_void_p(_lib.stream_handle(stream))))
+            if used < 0:
+                _lib.check(used, "tk_wire_pack_device_bias")
+        elif self.n_coded:
             used = int(self.lib.tk_wire_pack_device(self.recs, self.n_coded, self.src,
                                                     ctypes.c_void_p(self.wire.data_ptr()), self.bound,
                                                     ctypes.c_void_p(_lib.stream_handle(stream))))
@@ -199,6 +250,8 @@ class PackedCapture:
             for e in self.raw:
                 self.wire[used + e.raw_off:used + e.raw_off + e.raw_size].copy_(
                     _as_bytes(self.module.buffers[e.name]), non_blocking=True)
+            if self.addend_bytes:  # the values the packer has just read, in stream order
+                self.image[self.addend_off:self.wire_off].copy_(self.addends[:self.addend_bytes], non_blocking=True)
         self.copy_stream.wait_stream(stream)
         n = used + self.raw_bytes
         with torch.cuda.stream(self.copy_stream):
@@ -208,10 +261,11 @@ class PackedCapture:
             self._copy_events[1].record(self.copy_stream)
         # the head's variable fields: version, records_size; the section (the copy lands behind it)
         head = self.image.numpy()
-        section = tf.packed_section_head(self.entries, used)
-        head[8:16] = np.frombuffer(struct.pack("<Q", tf.PACKED_VERSION), np.uint8)
-        head[40:56] = np.frombuffer(struct.pack("<QQ", self.records_off, len(section) + n), np.uint8)
-        head[self.records_off:self.wire_off] = np.frombuffer(section, np.uint8)
+        section = tf.packed_section_head(self.entries, used, self.addend_bytes if self.bias else None)
+        version = tf.PACKED_BIAS_VERSION if self.bias else tf.PACKED_VERSION
+        head[8:16] = np.frombuffer(struct.pack("<Q", version), np.uint8)
+        head[40:56] = np.frombuffer(struct.pack("<QQ", self.records_off, len(section) + self.addend_bytes + n), np.uint8)
+        head[self.records_off:self.addend_off] = np.frombuffer(section, np.uint8)
         self.used, self.size = used, self.wire_off + n
         return self.size
 
@@ -366,13 +420,16 @@ class TraceVerifier:
         text = tf.header_json(meta)
         v1 = tf.TraceLayout.compute(text, self.params, self.records)
         head, records_off = tf.head_layout(text, self.params)
-        entries = tf.packed_entries(self.records)
+        # sized for either packed version: the version-3 plan and addends of the records the graph's
+        # rule selects (tk_wire_bound does not depend on the coding); a file that needs more grows it
+        entries = tf.packed_entries(self.records, bias_axes={i: a for i, (a, _) in PackedCapture.bias_records(plan).items()})
         recs, n = tf._wire_records(entries, [0] * len(entries))
         bound = int(self.lib.tk_wire_bound(recs, n)) if n else 0
         if bound < 0:
             _lib.check(bound, "tk_wire_bound")
         raw = sum(e.raw_size for e in entries)
-        packed = records_off + len(tf.packed_section_head(entries, 0)) + bound + raw
+        addends = tf.addend_bytes(entries)
+        packed = records_off + len(tf.packed_section_head(entries, 0, addends)) + addends + bound + raw
         # a file of the same graph from another job may carry a longer json: two pages of slack
         self._alloc(max(v1.total, packed) + 2 * self.ALIGN)
         self.uploads = 0  # H2D copies issued so far
@@ -380,7 +437,8 @@ class TraceVerifier:
     def _alloc(self, size: int) -> None:
         import torch
         self.staging = torch.empty(size, dtype=torch.uint8, pin_memory=True)
-        self.device = torch.empty(size + self.ALIGN, dtype=torch.uint8, device=self.module.device)
+        # (the params blob and a version-3 file's addends part are each rounded up to ALIGN on the device)
+        self.device = torch.empty(size + 2 * self.ALIGN, dtype=torch.uint8, device=self.module.device)
         self.host = self.staging.numpy()
 
     def _read(self, source) -> int:
@@ -417,7 +475,11 @@ class TraceVerifier:
         4 KiB boundary, so a packed file's wire is 64-byte aligned): one H2D copy each."""
         import torch
         self.params_at = 0
-        self.records_at = (ct.params_size + self.ALIGN - 1) // self.ALIGN * self.ALIGN
+        # (version 3: the addends part leads the records section; it is placed so that the wire
+        # behind it is at a 4 KiB boundary all the same)
+        self.wire_at = (ct.params_size + self.ALIGN - 1) // self.ALIGN * self.ALIGN + \
+            (ct.addend_size + self.ALIGN - 1) // self.ALIGN * self.ALIGN
+        self.records_at = self.wire_at - ct.addend_size
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         with torch.cuda.stream(stream):
             e0.record(stream)
@@ -434,12 +496,13 @@ class TraceVerifier:
 
     def _expected_ptr(self, ct, e) -> int:
         """Device address of a raw entry's payload."""
-        base = self.device.data_ptr() + self.records_at
+        base = self.device.data_ptr() + self.wire_at
         return base + (ct.wire_size if ct.packed else 0) + e.raw_off
 
     def _wire_call(self, ct, names, mode, stream):
-        """tk_wire_unpack_device over the coded records, with a destination for ``names`` only;
-        returns {name: (count, first)} in compare mode."""
+        """tk_wire_unpack_device over the coded records (version 3: tk_wire_unpack_device_bias, the
+        addends read from the uploaded addends part), with a destination for ``names`` only; returns
+        {name: (count, first)} in compare mode."""
         import ctypes
         coded = [e for e in ct.entries if e.coding != tf.RAW]
         if not coded:
@@ -447,9 +510,15 @@ class TraceVerifier:
         recs, n = tf._wire_records(ct.entries, [0] * len(ct.entries))
         dst = (ctypes.c_void_p * n)(*[self.module.buffers[e.name].data_ptr() if e.name in names else None for e in coded])
         report = (_lib.tk_wire_mismatch * n)()
-        _lib.check(self.lib.tk_wire_unpack_device(recs, n, ctypes.c_void_p(self.device.data_ptr() + self.records_at),
-                                                  ct.wire_size, dst, mode, report,
-                                                  ctypes.c_void_p(_lib.stream_handle(stream))), "tk_wire_unpack_device")
+        wire = ctypes.c_void_p(self.device.data_ptr() + self.wire_at)
+        if ct.version == tf.PACKED_BIAS_VERSION:
+            ads = tf._wire_addends(ct.entries, self.device.data_ptr() + self.records_at)
+            _lib.check(self.lib.tk_wire_unpack_device_bias(recs, ads, n, wire, ct.wire_size, dst, mode, report,
+                                                           ctypes.c_void_p(_lib.stream_handle(stream))),
+                       "tk_wire_unpack_device_bias")
+        else:
+            _lib.check(self.lib.tk_wire_unpack_device(recs, n, wire, ct.wire_size, dst, mode, report,
+                                                      ctypes.c_void_p(_lib.stream_handle(stream))), "tk_wire_unpack_device")
         return {e.name: (int(r.mismatches), int(r.first)) for e, r in zip(coded, report) if e.name in names}
 
     def _copy_raw(self, ct, names, stream) -> None:
@@ -652,6 +721,7 @@ class GraphModule:
         self.plan = module.plan
         self._capture: Optional[TraceCapture] = None
         self._packed: Optional[PackedCapture] = None
+        self._packed_bias: Optional[PackedCapture] = None
         self._verifier: Optional[TraceVerifier] = None
         self._accumulators: List[StatsAccumulator] = []
         self._one_shot: Dict[tuple, StatsAccumulator] = {}
@@ -677,9 +747,10 @@ class GraphModule:
         if self._capture is not None:
             self._capture.capture_stream.synchronize()
             self._capture = None
-        if self._packed is not None:
-            self._packed.copy_stream.synchronize()
-            self._packed = None
+        for cap in (self._packed, self._packed_bias):
+            if cap is not None:
+                cap.copy_stream.synchronize()
+        self._packed = self._packed_bias = None
         self._verifier = None
 
     def __enter__(self) -> "GraphModule":
@@ -776,7 +847,7 @@ class GraphModule:
                                           f"{a.dtype}{list(a.shape)} here")
             sel[name] = other.module.buffers[name]
         self.module.set_inputs(sel)
-        for cap in (self._capture, self._packed):
+        for cap in (self._capture, self._packed, self._packed_bias):
             if cap is not None:
                 cap.refresh_params([n for n in sel if n in cap.param_offsets])
 
@@ -851,7 +922,7 @@ class GraphModule:
                                           f"the graph expects {t.dtype}{list(t.shape)}")
             sel[name] = arr
         self.module.set_inputs(sel)
-        for cap in (self._capture, self._packed):
+        for cap in (self._capture, self._packed, self._packed_bias):
             if cap is not None:
                 cap.refresh_params([n for n in sel if n in cap.param_offsets])
 
@@ -867,18 +938,23 @@ class GraphModule:
             self._capture = TraceCapture(self.module, self._meta)
         return self._capture
 
-    def packed_capture(self) -> PackedCapture:
+    def packed_capture(self, bias: bool = False) -> PackedCapture:
+        if bias:
+            if self._packed_bias is None:
+                self._packed_bias = PackedCapture(self.module, self._meta, bias=True)
+            return self._packed_bias
         if self._packed is None:
             self._packed = PackedCapture(self.module, self._meta)
         return self._packed
 
     def set_trace_meta(self, **kw) -> None:
         self._meta.update(kw)
-        for cap in (self._capture, self._packed):
+        for cap in (self._capture, self._packed, self._packed_bias):
             if cap is not None:
                 cap.update_meta(**kw)
 
-    def dump_trace(self, path: str, sample_offset: Optional[int] = None, packed: bool = False) -> str:
+    def dump_trace(self, path: str, sample_offset: Optional[int] = None, packed: bool = False,
+                   bias: bool = False) -> str:
         """Write the trace of the last run (re-runs with capture if the last run was not traced).
 
         With ``packed`` the file is a packed (version 2) trace: the run is compute-only, the records
@@ -887,13 +963,20 @@ class GraphModule:
         trace image is captured and the host decoder is not used.  The staging is sized from
         tk_wire_bound when the first packed trace is dumped (PackedCapture), not grown on demand.
         trace_format.unpack_trace gives back exactly the file ``packed=False`` writes, and
-        trace_format.pack_trace of that file gives exactly this one."""
+        trace_format.pack_trace of that file gives exactly this one.
+
+        With ``packed`` and ``bias`` the file is version 3: the bias_add records are coded as the
+        record before them plus their bias, whose values the file stores (PackedCapture;
+        tk_wire_pack_device_bias).  pack_trace(bias=True) of the unpacked file gives exactly this
+        one wherever its data rule selects the same records, and every reader takes both versions."""
         import torch
+        if bias and not packed:
+            raise ValueError("dump_trace: bias coding is a coding of packed files (packed=True)")
         if sample_offset is not None:
             self.set_trace_meta(sample_offset=int(sample_offset))
         stream = torch.cuda.current_stream(self.module.device)
         if packed:
-            cap = self.packed_capture()
+            cap = self.packed_capture(bias)
             self.module.run(stream)
             cap.pack(stream)
             cap.synchronize()

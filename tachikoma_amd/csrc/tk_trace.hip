@@ -547,6 +547,11 @@ static int wire_pack_place_impl(const WireSegDev* segs, int64_t n_seg, void* wir
 // a 64-bit atomicMin on its first differing element, so an equal trace costs no atomic at all.  No
 // workgroup waits for another in either mode.
 //
+// kBias (tk_wire_unpack_device_bias, packed trace files of version 3): a table parallel to `segs`
+// gives each segment of a bias-coded record its addend (device), plane, channels and the host's
+// wire_seg_pos, and such a segment's element is predecessor + addend[channel] + base + offset.  The
+// two instantiations without it are compiled as before the switch existed.
+//
 // The host refuses a wire buffer tk_wire_check does not accept before it is uploaded; all the same a
 // workgroup holds every segment to wire_seg_extent's rules (start, header and stated length inside
 // the payload, widths the kind has) before it reads a header or a plane, and on failure sets the
@@ -556,9 +561,10 @@ enum { kWireStore = 0, kWireCompare = 1 };
 // (wire_report_mismatches, the workgroup's reduction and its two atomics, is in tk_common.h: the chain
 // check reports the same way)
 
-template <int kMode>
+template <int kMode, bool kBias>
 __global__ __launch_bounds__(256) void wire_decode_kernel(const WireUnitDev* __restrict__ units,
                                                           const WireSegOut* __restrict__ segs,
+                                                          const WireSegBias* __restrict__ bias,
                                                           const uint32_t* __restrict__ table,
                                                           const uint8_t* __restrict__ payload, int64_t payload_bytes,
                                                           tk_wire_mismatch* report, uint32_t* status) {
@@ -616,6 +622,8 @@ __global__ __launch_bounds__(256) void wire_decode_kernel(const WireUnitDev* __r
       return;
     }
     const WireSegOut so = segs[si];
+    WireSegBias sb{};
+    if constexpr (kBias) sb = bias[si];
     const uint64_t e_seg = (uint64_t)un.e0;
     uint32_t mis = 0, first = 0xFFFFFFFFu;  // the first differing element, counted within the segment
     if (bytes) {
@@ -706,8 +714,34 @@ __global__ __launch_bounds__(256) void wire_decode_kernel(const WireUnitDev* __r
           for (int j = 0; j < 16; ++j) c[j] |= wire_byte(o, j) << (8 * k);
         }
         const uint32_t base = (uint32_t)s_base[b];
+        bool walked = false;
+        if constexpr (kBias) {
+          // sb is the same for every thread.  The addend goes in with the base, in the one pass
+          // over the lane's 16 values, so no second array of them is live; the walk is
+          // wire_sub_addend's (it may pass the record's end, the channel stays one of the addend's)
+          if (sb.addend && m > 0) {
+            walked = true;
+            const uint32_t plane = (uint32_t)sb.plane, channels = (uint32_t)sb.channels;
+            const uint32_t t = (uint32_t)sb.r0 + (uint32_t)e0;
+            const uint32_t q = t / plane;
+            uint32_t r = t - q * plane;
+            uint32_t ch = ((uint32_t)sb.c0 + q) % channels;
+            uint32_t a = (uint32_t)sb.addend[ch] + base;
 #pragma unroll
-        for (int j = 0; j < 16; ++j) v[p][j] = (m > 0 ? v[p][j] : 0u) + base + c[j];  // int32 wrap-around
+            for (int j = 0; j < 16; ++j) {
+              v[p][j] += a + c[j];  // int32 wrap-around
+              if (++r == plane) {
+                r = 0;
+                ch = ch + 1 == channels ? 0 : ch + 1;
+                a = (uint32_t)sb.addend[ch] + base;
+              }
+            }
+          }
+        }
+        if (!walked) {
+#pragma unroll
+          for (int j = 0; j < 16; ++j) v[p][j] = (m > 0 ? v[p][j] : 0u) + base + c[j];  // int32 wrap-around
+        }
         if (!dst32 || valid <= 0) continue;
         if (aligned && valid == 16) {
 #pragma unroll
@@ -756,24 +790,31 @@ int wire_report_init(tk_wire_mismatch* report, int n, hipStream_t s) {
 }
 
 // `report` (device, n_report entries) is reset on the stream first; `status` (device) must be zero.
-static int wire_unpack_impl(const void* units, int64_t n_units, const void* segs, const void* wire, int64_t n_seg,
-                     int64_t wire_bytes, int mode, tk_wire_mismatch* report, int n_report, uint32_t* status,
-                     hipStream_t s) {
+template <int kMode, bool kBias>
+static void wire_decode_launch(const void* units, int64_t n_units, const void* segs, const void* bias, const void* wire,
+                               int64_t table, int64_t wire_bytes, tk_wire_mismatch* report, uint32_t* status,
+                               hipStream_t s) {
+  hipLaunchKernelGGL((wire_decode_kernel<kMode, kBias>), dim3((unsigned)n_units), dim3(256), 0, s,
+                     (const WireUnitDev*)units, (const WireSegOut*)segs, (const WireSegBias*)bias, (const uint32_t*)wire,
+                     (const uint8_t*)wire + table, wire_bytes - table, report, status);
+}
+
+// `bias` (device, a WireSegBias per segment) selects the instantiations that know addends; null: none.
+static int wire_unpack_impl(const void* units, int64_t n_units, const void* segs, const void* bias, const void* wire,
+                            int64_t n_seg, int64_t wire_bytes, int mode, tk_wire_mismatch* report, int n_report,
+                            uint32_t* status, hipStream_t s) {
   const int64_t table = wire_table_bytes(n_seg);
   TK_CHECK_ARG(units && segs && wire && status && n_units > 0 && n_units < ((int64_t)1 << 31) &&
                ((uintptr_t)wire & 63) == 0 && wire_bytes >= table && (mode == kWireStore || (report && n_report > 0)),
                "bad arguments");
-  const uint8_t* payload = (const uint8_t*)wire + table;
   if (mode == kWireStore) {
-    hipLaunchKernelGGL(wire_decode_kernel<kWireStore>, dim3((unsigned)n_units), dim3(256), 0, s,
-                       (const WireUnitDev*)units, (const WireSegOut*)segs, (const uint32_t*)wire, payload,
-                       wire_bytes - table, (tk_wire_mismatch*)nullptr, status);
+    if (bias) wire_decode_launch<kWireStore, true>(units, n_units, segs, bias, wire, table, wire_bytes, nullptr, status, s);
+    else wire_decode_launch<kWireStore, false>(units, n_units, segs, nullptr, wire, table, wire_bytes, nullptr, status, s);
   } else {
     hipLaunchKernelGGL(wire_report_init_kernel, dim3((unsigned)((n_report + 255) / 256)), dim3(256), 0, s, report, n_report);
     TK_LAUNCH_CHECK();
-    hipLaunchKernelGGL(wire_decode_kernel<kWireCompare>, dim3((unsigned)n_units), dim3(256), 0, s,
-                       (const WireUnitDev*)units, (const WireSegOut*)segs, (const uint32_t*)wire, payload,
-                       wire_bytes - table, report, status);
+    if (bias) wire_decode_launch<kWireCompare, true>(units, n_units, segs, bias, wire, table, wire_bytes, report, status, s);
+    else wire_decode_launch<kWireCompare, false>(units, n_units, segs, nullptr, wire, table, wire_bytes, report, status, s);
   }
   TK_LAUNCH_CHECK();
   return TK_OK;
@@ -971,13 +1012,19 @@ int tk_wire_encode_device_bias(const tk_wire_record* recs, const tk_wire_addend*
 
 int64_t tk_wire_pack_device(const tk_wire_record* recs, int n_recs, const void* const* src, void* wire,
                             int64_t wire_cap, void* stream) {
+  return tk_wire_pack_device_bias(recs, nullptr, n_recs, src, wire, wire_cap, stream);
+}
+
+int64_t tk_wire_pack_device_bias(const tk_wire_record* recs, const tk_wire_addend* addends, int n_recs,
+                                 const void* const* src, void* wire, int64_t wire_cap, void* stream) {
+  const std::string who = addends ? "tk_wire_pack_device_bias" : "tk_wire_pack_device";  // errors name the entry point called
   tk::WirePlan plan;
-  if (const int rc = tk::wire_plan(recs, n_recs, -1, "tk_wire_pack_device", &plan)) return rc;
+  if (const int rc = tk::wire_plan(recs, n_recs, -1, who.c_str(), &plan, addends)) return rc;
   if (!src || !wire || ((uintptr_t)wire & 63) != 0 || wire_cap < plan.bound) {
-    tk::set_error("tk_wire_pack_device: the wire buffer is not 64-byte aligned or smaller than tk_wire_bound");
+    tk::set_error(who + ": the wire buffer is not 64-byte aligned or smaller than tk_wire_bound");
     return TK_ERR_INVALID_ARG;
   }
-  const std::vector<tk::WireSegDev> segs = source_segs(plan, recs, src);
+  const std::vector<tk::WireSegDev> segs = source_segs(plan, recs, src, addends);
   const int64_t n_seg = (int64_t)segs.size();
   const int64_t table = tk::wire_table_bytes(n_seg);
   const int64_t seg_bytes = tk::wire_align(n_seg * (int64_t)sizeof(tk::WireSegDev), 64);
@@ -996,18 +1043,18 @@ int64_t tk_wire_pack_device(const tk_wire_record* recs, int n_recs, const void* 
   TK_HIP(hipMemcpyAsync(&total, scan + words - 1, sizeof(total), hipMemcpyDeviceToHost, s));
   TK_HIP(hipStreamSynchronize(s));
   if (total > 0xFFFFFFF0ull) {
-    tk::set_error("tk_wire_pack_device: the packed records do not fit the format's 32-bit segment starts");
+    tk::set_error(who + ": the packed records do not fit the format's 32-bit segment starts");
     return TK_ERR_UNSUPPORTED;
   }
   const int64_t used = table + 64 * (int64_t)total;
   if (used > plan.bound) {
-    tk::set_error("tk_wire_pack_device: the segment sizes exceed tk_wire_bound");
+    tk::set_error(who + ": the segment sizes exceed tk_wire_bound");
     return TK_ERR_HIP;
   }
   rc = tk::wire_pack_place_impl(dev_segs, n_seg, wire, used, s);
   if (rc != TK_OK) return rc;
   if (hipStreamSynchronize(s) != hipSuccess) {
-    tk::set_error("tk_wire_pack_device: the place kernel failed");
+    tk::set_error(who + ": the place kernel failed");
     return TK_ERR_HIP;
   }
   return used;
@@ -1017,24 +1064,31 @@ int tk_wire_pack_tile(void) { return tk::kWireScanTile; }
 
 int tk_wire_unpack_device(const tk_wire_record* recs, int n_recs, const void* wire, int64_t wire_bytes,
                           void* const* dst, int mode, tk_wire_mismatch* report, void* stream) {
+  return tk_wire_unpack_device_bias(recs, nullptr, n_recs, wire, wire_bytes, dst, mode, report, stream);
+}
+
+int tk_wire_unpack_device_bias(const tk_wire_record* recs, const tk_wire_addend* addends, int n_recs, const void* wire,
+                               int64_t wire_bytes, void* const* dst, int mode, tk_wire_mismatch* report,
+                               void* stream) {
+  const std::string who = addends ? "tk_wire_unpack_device_bias" : "tk_wire_unpack_device";  // errors name the entry point called
   tk::WirePlan plan;
-  if (const int rc = tk::wire_plan(recs, n_recs, -1, "tk_wire_unpack_device", &plan)) return rc;
+  if (const int rc = tk::wire_plan(recs, n_recs, -1, who.c_str(), &plan, addends)) return rc;
   const bool compare = mode == TK_WIRE_UNPACK_COMPARE;
   if (!wire || !dst || ((uintptr_t)wire & 63) != 0 || (mode != TK_WIRE_UNPACK_STORE && !compare) ||
       (compare && !report)) {
-    tk::set_error("tk_wire_unpack_device: null argument, unknown mode or a wire buffer that is not 64-byte aligned");
+    tk::set_error(who + ": null argument, unknown mode or a wire buffer that is not 64-byte aligned");
     return TK_ERR_INVALID_ARG;
   }
   for (int i = 0; i < n_recs; ++i)
-    if (recs[i].kind == tk::kWireI32 && ((uintptr_t)dst[i] & 3) != 0) {
-      tk::set_error("tk_wire_unpack_device: the buffer of int32 record " + std::to_string(i) + " is not 4-byte aligned");
+    if (tk::wire_seg_kind(recs[i].kind) == tk::kWireI32 && ((uintptr_t)dst[i] & 3) != 0) {
+      tk::set_error(who + ": the buffer of int32 record " + std::to_string(i) + " is not 4-byte aligned");
       return TK_ERR_INVALID_ARG;
     }
   const std::vector<tk::WireSegRef>& refs = plan.segs;
   const std::vector<tk::WireUnit>& units = plan.units;
   const int64_t n_seg = (int64_t)refs.size(), n_units = (int64_t)units.size();
   if (wire_bytes < tk::wire_table_bytes(n_seg)) {
-    tk::set_error("tk_wire_unpack_device: the segment table does not lie inside the wire buffer");
+    tk::set_error(who + ": the segment table does not lie inside the wire buffer");
     return TK_ERR_INVALID_ARG;
   }
   std::vector<tk::WireSegOut> segs(refs.size());
@@ -1043,32 +1097,43 @@ int tk_wire_unpack_device(const tk_wire_record* recs, int n_recs, const void* wi
   std::vector<tk::WireUnitDev> udev(units.size());
   for (size_t u = 0; u < units.size(); ++u) {
     const tk::WireSegRef& r = refs[units[u].first];
-    udev[u] = {units[u].first, units[u].stride, units[u].count, r.n, recs[r.rec].kind, 0, r.e0};
+    udev[u] = {units[u].first, units[u].stride, units[u].count, r.n, tk::wire_seg_kind(recs[r.rec].kind), 0, r.e0};
   }
+  // the bias table (and with it the instantiations that read one) only where a record has an addend
+  std::vector<tk::WireSegBias> bias;
+  for (size_t i = 0; i < refs.size(); ++i)
+    if (const tk_wire_addend* ad = tk::wire_addend_of(recs, addends, refs[i].rec)) {
+      if (bias.empty()) bias.resize(refs.size());
+      tk::wire_seg_bias(&bias[i], ad->addend, ad->plane, ad->channels, refs[i].e0);
+    }
   const int64_t seg_bytes = tk::wire_align(n_seg * (int64_t)sizeof(tk::WireSegOut), 64);
   const int64_t unit_bytes = tk::wire_align(n_units * (int64_t)sizeof(tk::WireUnitDev), 64);
   const int64_t rep_bytes = tk::wire_align((int64_t)n_recs * (int64_t)sizeof(tk_wire_mismatch), 64);
+  const int64_t bias_bytes = tk::wire_align((int64_t)bias.size() * (int64_t)sizeof(tk::WireSegBias), 64);
   hipStream_t s = tk::as_stream(stream);
   std::lock_guard<std::mutex> lock(g_unpack_scratch.mu);
   char* dev = nullptr;
-  int rc = g_unpack_scratch.reserve(seg_bytes + unit_bytes + rep_bytes + 64, &dev);
+  int rc = g_unpack_scratch.reserve(seg_bytes + unit_bytes + rep_bytes + 64 + bias_bytes, &dev);
   if (rc != TK_OK) return rc;
+  char* dev_bias = bias.empty() ? nullptr : dev + seg_bytes + unit_bytes + rep_bytes + 64;
+  if (dev_bias)
+    TK_HIP(hipMemcpyAsync(dev_bias, bias.data(), bias.size() * sizeof(tk::WireSegBias), hipMemcpyHostToDevice, s));
   tk_wire_mismatch* rep = (tk_wire_mismatch*)(dev + seg_bytes + unit_bytes);
   uint32_t* status = (uint32_t*)(dev + seg_bytes + unit_bytes + rep_bytes);
   TK_HIP(hipMemcpyAsync(dev, segs.data(), segs.size() * sizeof(tk::WireSegOut), hipMemcpyHostToDevice, s));
   TK_HIP(hipMemcpyAsync(dev + seg_bytes, udev.data(), udev.size() * sizeof(tk::WireUnitDev), hipMemcpyHostToDevice, s));
   TK_HIP(hipMemsetAsync(status, 0, sizeof(uint32_t), s));
-  rc = tk::wire_unpack_impl(dev + seg_bytes, n_units, dev, wire, n_seg, wire_bytes, mode, rep, n_recs, status, s);
+  rc = tk::wire_unpack_impl(dev + seg_bytes, n_units, dev, dev_bias, wire, n_seg, wire_bytes, mode, rep, n_recs, status, s);
   if (rc != TK_OK) return rc;
   uint32_t bad = 0;
   if (compare) TK_HIP(hipMemcpyAsync(report, rep, (size_t)n_recs * sizeof(tk_wire_mismatch), hipMemcpyDeviceToHost, s));
   TK_HIP(hipMemcpyAsync(&bad, status, sizeof(bad), hipMemcpyDeviceToHost, s));
   if (hipStreamSynchronize(s) != hipSuccess) {
-    tk::set_error("tk_wire_unpack_device: the decode kernel failed");
+    tk::set_error(who + ": the decode kernel failed");
     return TK_ERR_HIP;
   }
   if (bad) {
-    tk::set_error("tk_wire_unpack_device: a segment does not lie inside the wire buffer or states a width its kind "
+    tk::set_error(who + ": a segment does not lie inside the wire buffer or states a width its kind "
                   "does not have (was the buffer checked with tk_wire_check?)");
     return TK_ERR_INVALID_ARG;
   }

@@ -494,20 +494,28 @@ int tk_wire_decode_bias(const tk_wire_record* recs, const tk_wire_addend* addend
 }
 
 int tk_wire_check(const tk_wire_record* recs, int n_recs, const void* wire, int64_t wire_bytes) {
+  return tk_wire_check_bias(recs, nullptr, n_recs, wire, wire_bytes);
+}
+
+// The addends are looked at as wire_plan looks at them (pointer, plane, channels): no value is read.
+int tk_wire_check_bias(const tk_wire_record* recs, const tk_wire_addend* addends, int n_recs, const void* wire,
+                       int64_t wire_bytes) {
+  const std::string who = addends ? "tk_wire_check_bias" : "tk_wire_check";  // errors name the entry point called
   tk::WirePlan p;
-  if (const int rc = tk::wire_plan(recs, n_recs, -1, "tk_wire_check", &p)) return rc;
+  if (const int rc = tk::wire_plan(recs, n_recs, -1, who.c_str(), &p, addends)) return rc;
   const int64_t n_seg = (int64_t)p.segs.size();
   const int64_t table = tk::wire_table_bytes(n_seg);
   if (!wire || wire_bytes < table) {
-    tk::set_error("tk_wire_check: the segment table does not lie inside the wire buffer");
+    tk::set_error(who + ": the segment table does not lie inside the wire buffer");
     return TK_ERR_INVALID_ARG;
   }
   const char* payload = (const char*)wire + table;
   for (int64_t i = 0; i < n_seg; ++i) {
     uint32_t start;
     std::memcpy(&start, (const char*)wire + 4 * i, 4);
-    if (tk::wire_seg_extent(recs[p.segs[i].rec].kind, p.segs[i].n, start, payload, wire_bytes - table) < 0) {
-      tk::set_error("tk_wire_check: segment " + std::to_string(i) + " (record " + std::to_string(p.segs[i].rec) +
+    if (tk::wire_seg_extent(tk::wire_seg_kind(recs[p.segs[i].rec].kind), p.segs[i].n, start, payload,
+                            wire_bytes - table) < 0) {
+      tk::set_error(who + ": segment " + std::to_string(i) + " (record " + std::to_string(p.segs[i].rec) +
                     ") does not lie inside the wire buffer or states a width its kind does not have");
       return TK_ERR_INVALID_ARG;
     }

@@ -59,7 +59,9 @@ inline int64_t wire_header_bytes(int nb) { return wire_align(4 * (int64_t)nb, 16
 // element kind of a record / segment (tk_wire_record.kind)
 enum WireKind : int32_t { kWireI32 = 0, kWireI8 = 1, kWireU8 = 2, kWireI32Bias = 3 };
 // A record of kind kWireI32Bias is an int32 record coded with an addend (tk_wire_addend); its
-// segments are int32 segments (kWireI32) that carry the addend.
+// segments are int32 segments (kWireI32) that carry the addend.  Packed trace files of format
+// version 3 store such records with their addend values; the entry points behind them are
+// tk_wire_check_bias, tk_wire_pack_device_bias and tk_wire_unpack_device_bias.
 inline int wire_seg_kind(int kind) { return kind == kWireI32Bias ? (int)kWireI32 : kind; }
 inline int wire_elem_bytes(int kind) { return wire_seg_kind(kind) == kWireI32 ? 4 : 1; }
 // worst case (every block raw) of a segment of n elements of esize bytes
@@ -89,6 +91,12 @@ struct WireSegOut {
   void* dst;  // the segment's first element in the record's buffer (device), or null
   int32_t rec;
   int32_t pad;
+};
+// the bias coding of a segment, in a table parallel to WireSegOut (tk_wire_unpack_device_bias)
+struct WireSegBias {
+  const int32_t* addend = nullptr;  // device, `channels` values; null: the segment has no addend
+  int32_t plane = 0, channels = 0;
+  int32_t c0 = 0, r0 = 0;           // wire_seg_pos of the segment's first element
 };
 struct WireUnitDev {
   int32_t first, stride, count;  // segments first, first + stride, ...
@@ -144,7 +152,7 @@ struct WirePlan {
 // or kind (kinds 0 and 3 chain with each other), a record of kind 3 that is not differenced, has
 // 2^31 elements or more, or whose addends[i] has no addend or a plane or channels below 1, 2^31
 // segments or more: sets the error under `who`'s name and returns the status.  `addends` null (every
-// entry point without addends; packed trace files, the device decoder): kind 3 is refused
+// entry point without addends; packed trace files of version 2 and their device decoder): kind 3 is refused
 // (TK_ERR_UNSUPPORTED) unless `bias_ok` (tk_wire_bound: the size does not depend on the addend).
 int wire_plan(const tk_wire_record* recs, int n_recs, int64_t image_bytes, const char* who, WirePlan* plan,
               const tk_wire_addend* addends = nullptr, bool bias_ok = false);

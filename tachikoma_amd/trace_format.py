@@ -197,7 +197,7 @@ def read_trace(path_or_bytes, copy: bool = False) -> Trace:
     """The trace of a file of either version (a packed file is expanded first: unpack_trace)."""
     buf = _open(path_or_bytes)
     version, jl, po, ps, ro, rs = _header(buf)
-    if version == PACKED_VERSION:
+    if version in PACKED_VERSIONS:
         buf = unpack_trace(buf)
         version, jl, po, ps, ro, rs = _header(buf)
     if version != TRACE_VERSION:
@@ -293,11 +293,36 @@ def trace_bytes(meta: Dict[str, Any], params: Dict[str, np.ndarray], records: Di
 # Nothing is padded beyond 8 bytes: a packed file is never larger than the version-1 file plus the
 # wire's worst case (tk_wire_bound) minus the bytes of the coded records.
 
+# Version 3 adds the bias coding of the wire (coding 3: an int32 record coded as the record before
+# it plus a per-channel addend, include/tachikoma.h).  It is opt-in (pack_trace(bias=True),
+# GraphModule.dump_trace(packed=True, bias=True)); the section header grows by one field and the
+# addend values lie in the file, in a part of their own in front of the wire:
+#
+#     u32 "TKPK" | u32 n_records | u64 plan_len | u64 wire_size | u64 raw_size | u64 addend_size
+#     plan       as version 2; an entry with coding 3 (dtype int32, diff 1) is followed by
+#                u8 axis, u64 addend_off   (byte offset into the addends part, a multiple of 4)
+#     pad to 8
+#     addends    int32 values, channels = shape[axis] of them per coding-3 entry; padded to 8
+#     wire       what tk_wire_encode_host_bias writes
+#     raw
+#
+# `plane` is the product of the dims behind `axis`.  The file is self-contained: a reader follows the
+# stored plan and the stored addend values and never looks at the graph or the params blob for them.
+
 PACKED_VERSION = 2
+PACKED_BIAS_VERSION = 3
+PACKED_VERSIONS = (PACKED_VERSION, PACKED_BIAS_VERSION)
 PACK_MAGIC = 0x4B504B54  # "TKPK"
 RAW = 255
+BIAS = 3  # coding of a bias-coded int32 record (version 3 only)
 WIRE_KIND = {"int32": 0, "int8": 1, "uint8": 2}
 _SECTION = struct.Struct("<IIQQQ")
+_SECTION3 = struct.Struct("<IIQQQQ")
+
+
+def _seg_kind(coding: int) -> int:
+    """The element kind a coding's segments have: a bias-coded record is an int32 record."""
+    return 0 if coding == BIAS else coding
 
 
 def _align(x: int, a: int) -> int:
@@ -338,23 +363,71 @@ class PackedEntry:
     diff: int
     raw_off: int = 0
     raw_size: int = 0
+    axis: int = 0          # coding 3: the bias axis, and where its addend lies in the addends part
+    addend_off: int = 0
 
     @property
     def nbytes(self) -> int:
         return _n_elems(self.shape) * np.dtype(self.dtype).itemsize
 
+    @property
+    def channels(self) -> int:
+        return int(self.shape[self.axis])
 
-def packed_entries(records, plan=None) -> List[PackedEntry]:
-    """Plan entries of a record list (raw payloads laid out in trace order)."""
+    @property
+    def plane(self) -> int:
+        return _n_elems(self.shape[self.axis + 1:])
+
+
+def packed_entries(records, plan=None, bias_axes=None) -> List[PackedEntry]:
+    """Plan entries of a record list (raw payloads laid out in trace order).  ``bias_axes`` (version
+    3): {record index: axis} of the records to bias-code, each of which the rule differences; their
+    addends are laid out in trace order."""
     plan = plan_records(records) if plan is None else plan
-    out, raw = [], 0
-    for (name, shape, dtype), (coding, diff) in zip(records, plan):
+    out, raw, add = [], 0, 0
+    for i, ((name, shape, dtype), (coding, diff)) in enumerate(zip(records, plan)):
         e = PackedEntry(name, tuple(int(d) for d in shape), str(np.dtype(dtype)), int(coding), int(diff))
         if coding == RAW:
             e.raw_off, e.raw_size = raw, e.nbytes
             raw += e.raw_size
+        if bias_axes and i in bias_axes:
+            if (e.coding, e.diff) != (0, 1) or not 0 <= bias_axes[i] < len(e.shape) or _n_elems(e.shape) >= 1 << 31:
+                raise ValueError(f"record {name} cannot be bias-coded: not a differenced int32 record of fewer than "
+                                 f"2^31 elements with the axis {bias_axes[i]}")
+            e.coding, e.axis, e.addend_off = BIAS, int(bias_axes[i]), add
+            add += 4 * e.channels
         out.append(e)
     return out
+
+
+def addend_bytes(entries: Sequence[PackedEntry]) -> int:
+    """Size of the addends part of a version-3 file with these entries (padded to 8)."""
+    return _align(sum(4 * e.channels for e in entries if e.coding == BIAS), 8)
+
+
+def bias_axes_of_data(records: "Dict[str, np.ndarray]", plan=None) -> Tuple[Dict[int, int], Dict[int, np.ndarray]]:
+    """The host packer's rule for the bias coding, ({record index: axis}, {record index: addend}).  It
+    has no graph, so the rule is the data's: a record the version-2 rule differences, of rank >= 2
+    and fewer than 2^31 elements, is bias-coded with axis 1 when ``rec - prev`` (int32 wrap-around)
+    is constant over every (sample, channel) plane, with one constant per channel across all
+    samples; that constant is the addend.  For a trace the engine wrote this selects every bias_add
+    record (GraphModule.dump_trace(packed=True, bias=True) selects those by the graph), and others
+    only for degenerate data: a record that happens to differ from the one before it by a constant
+    per channel, e.g. where both are constant on every plane.  Any selection round-trips; it only
+    decides how small the file is."""
+    items = [(k, v.shape, str(v.dtype)) for k, v in records.items()]
+    plan = plan_records(items) if plan is None else plan
+    arrays = list(records.values())
+    axes, addends = {}, {}
+    for i, (coding, diff) in enumerate(plan):
+        v = arrays[i]
+        if (coding, diff) != (0, 1) or v.ndim < 2 or v.size >= 1 << 31:
+            continue
+        d = (v.view("<u4") - arrays[i - 1].view("<u4")).reshape(v.shape[0], v.shape[1], -1)
+        add = d[0, :, 0]
+        if np.array_equal(d, np.broadcast_to(add[None, :, None], d.shape)):
+            axes[i], addends[i] = 1, add.view("<i4").copy()
+    return axes, addends
 
 
 def _plan_bytes(entries: Sequence[PackedEntry]) -> bytes:
@@ -366,10 +439,12 @@ def _plan_bytes(entries: Sequence[PackedEntry]) -> bytes:
         out += struct.pack(f"<{len(e.shape)}q", *e.shape)
         if e.coding == RAW:
             out += struct.pack("<QQ", e.raw_off, e.raw_size)
+        elif e.coding == BIAS:
+            out += struct.pack("<BQ", e.axis, e.addend_off)
     return bytes(out)
 
 
-def _parse_plan(mv, off: int, end: int, n: int) -> List[PackedEntry]:
+def _parse_plan(mv, off: int, end: int, n: int, version: int = PACKED_VERSION) -> List[PackedEntry]:
     entries = []
     for _ in range(n):
         if off + 2 > end:
@@ -381,7 +456,8 @@ def _parse_plan(mv, off: int, end: int, n: int) -> List[PackedEntry]:
         name = bytes(mv[off:off + ln]).decode()
         code, bits, ndim, coding, diff = struct.unpack_from("<5B", mv, off + ln)
         off += ln + 5
-        if off + 8 * ndim + (16 if coding == RAW else 0) > end:
+        extra = 16 if coding == RAW else 9 if coding == BIAS and version == PACKED_BIAS_VERSION else 0
+        if off + 8 * ndim + extra > end:
             raise ValueError("truncated coding plan")
         shape = struct.unpack_from(f"<{ndim}q", mv, off)
         off += 8 * ndim
@@ -391,6 +467,9 @@ def _parse_plan(mv, off: int, end: int, n: int) -> List[PackedEntry]:
         if coding == RAW:
             e.raw_off, e.raw_size = struct.unpack_from("<QQ", mv, off)
             off += 16
+        elif extra:
+            e.axis, e.addend_off = struct.unpack_from("<BQ", mv, off)
+            off += 9
         entries.append(e)
     return entries
 
@@ -404,11 +483,26 @@ def _wire_records(entries: Sequence[PackedEntry], offsets: Sequence[int]):
     return arr, len(coded)
 
 
-def packed_section_head(entries: Sequence[PackedEntry], wire_size: int) -> bytes:
-    """The records section of a packed file up to the wire: section header, plan, pad to 8."""
+def _wire_addends(entries: Sequence[PackedEntry], base: int):
+    """tk_wire_addend array beside _wire_records': the addends part starts at address ``base`` (host
+    or device, as the entry point reads it)."""
+    coded = [e for e in entries if e.coding != RAW]
+    arr = (_lib.tk_wire_addend * max(1, len(coded)))()
+    for i, e in enumerate(coded):
+        if e.coding == BIAS:
+            arr[i].plane, arr[i].channels, arr[i].addend = e.plane, e.channels, base + e.addend_off
+    return arr
+
+
+def packed_section_head(entries: Sequence[PackedEntry], wire_size: int, addend_size: Optional[int] = None) -> bytes:
+    """The records section of a packed file up to the wire (version 2) or up to the addends part
+    (version 3: ``addend_size`` given): section header, plan, pad to 8."""
     plan = _plan_bytes(entries)
     raw_size = sum(e.raw_size for e in entries)
-    head = _SECTION.pack(PACK_MAGIC, len(entries), len(plan), wire_size, raw_size) + plan
+    if addend_size is None:
+        head = _SECTION.pack(PACK_MAGIC, len(entries), len(plan), wire_size, raw_size) + plan
+    else:
+        head = _SECTION3.pack(PACK_MAGIC, len(entries), len(plan), wire_size, raw_size, addend_size) + plan
     return head + b"\0" * (_align(len(head), 8) - len(head))
 
 
@@ -417,10 +511,15 @@ def _ptr(buf) -> Tuple[int, np.ndarray]:
     return a.ctypes.data, a
 
 
-def pack_trace(path_or_bytes) -> bytes:
+def pack_trace(path_or_bytes, bias: bool = False) -> bytes:
     """The host packer: the packed (version 2) file of a version-1 trace file, built on
     tk_wire_encode_host.  Compresses existing files without a GPU, and gives byte for byte what
-    GraphModule.dump_trace(packed=True) writes for the same run."""
+    GraphModule.dump_trace(packed=True) writes for the same run.
+
+    With ``bias`` the file is version 3: the records bias_axes_of_data selects (for a trace the
+    engine wrote: the bias_add records; others only for degenerate data, see there) are bias-coded
+    and their addends stored, and the file is byte for byte what
+    GraphModule.dump_trace(packed=True, bias=True) writes wherever the two select the same records."""
     buf = _open(path_or_bytes)
     version, jl, po, ps, ro, rs = _header(buf)
     if version != TRACE_VERSION:
@@ -432,7 +531,11 @@ def pack_trace(path_or_bytes) -> bytes:
     base, keep = _ptr(buf)
     items = [(k, v.shape, str(v.dtype)) for k, v in records.items()]
     offsets = [(v.ctypes.data - base) if v.size else ro for v in records.values()]
-    entries = packed_entries(items)
+    axes, values = bias_axes_of_data(records) if bias else ({}, {})
+    entries = packed_entries(items, bias_axes=axes)
+    addends = np.zeros(addend_bytes(entries) // 4, "<i4")
+    for i, v in values.items():
+        addends[entries[i].addend_off // 4:entries[i].addend_off // 4 + v.size] = v
     recs, n = _wire_records(entries, offsets)
     wire = b""
     if n:
@@ -440,15 +543,21 @@ def pack_trace(path_or_bytes) -> bytes:
         if bound < 0:
             _lib.check(int(bound), "tk_wire_bound")
         out = np.empty(bound, np.uint8)
-        used = lib.tk_wire_encode_host(recs, n, ctypes.c_void_p(base), len(buf), ctypes.c_void_p(out.ctypes.data), bound)
+        if bias:
+            used = lib.tk_wire_encode_host_bias(recs, _wire_addends(entries, addends.ctypes.data), n, ctypes.c_void_p(base),
+                                                len(buf), ctypes.c_void_p(out.ctypes.data), bound)
+        else:
+            used = lib.tk_wire_encode_host(recs, n, ctypes.c_void_p(base), len(buf), ctypes.c_void_p(out.ctypes.data),
+                                           bound)
         if used < 0:
             _lib.check(int(used), "tk_wire_encode_host")
         wire = out[:used].tobytes()
-    head = packed_section_head(entries, len(wire))
+    head = packed_section_head(entries, len(wire), addends.nbytes if bias else None)
     raws = [v.tobytes() for e, v in zip(entries, records.values()) if e.coding == RAW]
-    section = head + wire + b"".join(raws)
+    section = head + (addends.tobytes() if bias else b"") + wire + b"".join(raws)
     del keep
-    return (struct.pack("<7Q", TRACE_MAGIC, PACKED_VERSION, jl, po, ps, ro, len(section)) + bytes(buf[56:ro]) + section)
+    version = PACKED_BIAS_VERSION if bias else PACKED_VERSION
+    return (struct.pack("<7Q", TRACE_MAGIC, version, jl, po, ps, ro, len(section)) + bytes(buf[56:ro]) + section)
 
 
 @dataclass
@@ -463,36 +572,56 @@ class PackedFile:
     raw_off: int
     raw_size: int
     size: int
+    version: int = PACKED_VERSION
+    addend_off: int = 0    # version 3: the addends part (it ends where the wire starts)
+    addend_size: int = 0
 
 
 def parse_packed(buf) -> PackedFile:
-    """Header, sections and coding plan of a packed file, every extent checked against the buffer."""
+    """Header, sections and coding plan of a packed file (version 2 or 3), every extent checked
+    against the buffer."""
     version, jl, po, ps, ro, rs = _header(buf)
-    if version != PACKED_VERSION:
-        raise ValueError(f"not a packed (version {PACKED_VERSION}) trace: version {version}")
+    if version not in PACKED_VERSIONS:
+        raise ValueError(f"not a packed (version {PACKED_VERSION} or {PACKED_BIAS_VERSION}) trace: version {version}")
+    v3 = version == PACKED_BIAS_VERSION
+    section = _SECTION3 if v3 else _SECTION
     size = len(buf)
-    if not 56 + jl <= po <= po + ps <= ro <= ro + rs <= size or rs < _SECTION.size:
+    if not 56 + jl <= po <= po + ps <= ro <= ro + rs <= size or rs < section.size:
         raise ValueError("truncated packed trace file")
     try:
         json_text = bytes(buf[56:56 + jl]).decode()
-        magic, n, plan_len, wire_size, raw_size = _SECTION.unpack_from(buf, ro)
+        magic, n, plan_len, wire_size, raw_size, *rest = section.unpack_from(buf, ro)
+        addend_size = rest[0] if v3 else 0
         if magic != PACK_MAGIC:
             raise ValueError("packed trace: bad records section")
-        wire_off = ro + _align(_SECTION.size + plan_len, 8)
-        if wire_off + wire_size + raw_size != ro + rs or n > plan_len:
+        addend_off = ro + _align(section.size + plan_len, 8)
+        wire_off = addend_off + addend_size
+        if wire_off + wire_size + raw_size != ro + rs or n > plan_len or addend_size % 8:
             raise ValueError("truncated packed trace file (sections do not add up)")
-        entries = _parse_plan(memoryview(buf), ro + _SECTION.size, ro + _SECTION.size + plan_len, n)
+        entries = _parse_plan(memoryview(buf), ro + section.size, ro + section.size + plan_len, n, version)
     except (struct.error, UnicodeDecodeError) as e:
         raise ValueError(f"packed trace: {e}") from None
     for i, e in enumerate(entries):
         if e.coding == RAW:
             if e.raw_size != e.nbytes or e.raw_off + e.raw_size > raw_size:
                 raise ValueError(f"record {e.name}: raw payload outside the file")
+            continue
+        before = entries[i - 1] if i else None
+        if e.coding == BIAS and v3:
+            if (e.diff != 1 or e.dtype != "int32" or not 1 <= _n_elems(e.shape) < 1 << 31 or before is None or
+                    _seg_kind(before.coding) != 0 or _n_elems(before.shape) != _n_elems(e.shape)):
+                raise ValueError(f"record {e.name}: bias coding of a record that is not a differenced int32 record of "
+                                 f"fewer than 2^31 elements after a coded int32 record of the same element count")
+            if e.axis >= len(e.shape) or e.shape[e.axis] < 1:
+                raise ValueError(f"record {e.name}: bias axis {e.axis} is not an axis of shape {list(e.shape)}")
+            if e.addend_off % 4 or e.addend_off + 4 * e.channels > addend_size:
+                raise ValueError(f"record {e.name}: its addends do not lie inside the addends part")
         elif (WIRE_KIND.get(e.dtype) != e.coding or not 1 <= _n_elems(e.shape) <= 1 << 40 or e.diff not in (0, 1) or
-              (e.diff and (i == 0 or entries[i - 1].coding != e.coding or
-                           _n_elems(entries[i - 1].shape) != _n_elems(e.shape)))):
+              (e.diff and (before is None or (_seg_kind(before.coding) if v3 else before.coding) != e.coding or
+                           _n_elems(before.shape) != _n_elems(e.shape)))):
             raise ValueError(f"record {e.name}: coding {e.coding} / diff {e.diff} does not fit the record list")
-    return PackedFile(json_text, po, ps, entries, wire_off, wire_size, wire_off + wire_size, raw_size, size)
+    return PackedFile(json_text, po, ps, entries, wire_off, wire_size, wire_off + wire_size, raw_size, size,
+                      int(version), addend_off, addend_size)
 
 
 def unpack_trace(path_or_bytes) -> bytearray:
@@ -526,8 +655,14 @@ def unpack_trace(path_or_bytes) -> bytearray:
         recs, n = _wire_records(pf.entries, layout.record_offsets)
         if n:
             base, keep = _ptr(buf)
-            rc = lib.tk_wire_decode(recs, n, ctypes.c_void_p(base + pf.wire_off), pf.wire_size,
-                                    ctypes.c_void_p(ctypes.addressof(cbuf)), len(image), 0)
+            if pf.version == PACKED_BIAS_VERSION:
+                # (the addends part is 8-byte aligned in the file; mapped or copied, in memory too)
+                rc = lib.tk_wire_decode_bias(recs, _wire_addends(pf.entries, base + pf.addend_off), n,
+                                             ctypes.c_void_p(base + pf.wire_off), pf.wire_size,
+                                             ctypes.c_void_p(ctypes.addressof(cbuf)), len(image), 0)
+            else:
+                rc = lib.tk_wire_decode(recs, n, ctypes.c_void_p(base + pf.wire_off), pf.wire_size,
+                                        ctypes.c_void_p(ctypes.addressof(cbuf)), len(image), 0)
             del keep
             if rc != 0:
                 raise ValueError("packed trace: " + lib.tk_last_error().decode(errors="replace"))
@@ -552,14 +687,15 @@ class CheckedTrace:
     params: List[Tuple[str, Tuple[int, ...], str, int]]   # name, shape, dtype, absolute payload offset
     params_off: int
     params_size: int
-    records_off: int      # packed: the wire's first byte; version 1: the records blob
-    records_size: int     # packed: wire + raw; version 1: the blob
+    records_off: int      # packed: the wire's first byte (version 3: the addends part's); version 1: the records blob
+    records_size: int     # packed: [addends +] wire + raw; version 1: the blob
     wire_size: int        # 0 in a version-1 file
     size: int
+    addend_size: int = 0  # version 3: the addends part, which the wire follows
 
     @property
     def packed(self) -> bool:
-        return self.version == PACKED_VERSION
+        return self.version in PACKED_VERSIONS
 
 
 def _list_items(buf, off: int, size: int):
@@ -582,7 +718,8 @@ def check_trace(buf, records, params=None) -> CheckedTrace:
     truncated file, a plan or a wire table that does not hold, or a trace of another graph (or of
     another batch size, which is another record list)."""
     version = _header(buf)[0]
-    if version == PACKED_VERSION:
+    addend_size = 0
+    if version in PACKED_VERSIONS:
         pf = parse_packed(buf)
         try:
             meta = json.loads(pf.json_text)
@@ -593,13 +730,19 @@ def check_trace(buf, records, params=None) -> CheckedTrace:
         if n:
             base, keep = _ptr(buf)
             lib = _lib.load()
-            rc = lib.tk_wire_check(recs, n, ctypes.c_void_p(base + pf.wire_off), pf.wire_size)
+            if version == PACKED_BIAS_VERSION:
+                rc = lib.tk_wire_check_bias(recs, _wire_addends(entries, base + pf.addend_off), n,
+                                            ctypes.c_void_p(base + pf.wire_off), pf.wire_size)
+            else:
+                rc = lib.tk_wire_check(recs, n, ctypes.c_void_p(base + pf.wire_off), pf.wire_size)
             del keep
             if rc != 0:
                 raise ValueError("packed trace: " + lib.tk_last_error().decode(errors="replace"))
         elif pf.wire_size:
             raise ValueError("packed trace: a wire buffer without coded records")
-        records_off, records_size, wire_size = pf.wire_off, pf.wire_size + pf.raw_size, pf.wire_size
+        addend_size = pf.addend_size
+        records_off, records_size = pf.wire_off - addend_size, addend_size + pf.wire_size + pf.raw_size
+        wire_size = pf.wire_size
     elif version == TRACE_VERSION:
         _, jl, po, ps, ro, rs = _header(buf)
         if not 56 + jl <= po <= po + ps <= ro <= ro + rs <= len(buf):
@@ -633,17 +776,22 @@ def check_trace(buf, records, params=None) -> CheckedTrace:
         want_p = sorted((n, tuple(int(d) for d in s), str(np.dtype(d))) for n, s, d in params)
         if sorted(p[:3] for p in p_items) != want_p:
             raise ValueError("trace is of another graph: its params are not the graph's")
-    return CheckedTrace(int(version), meta, list(entries), p_items, po, ps, records_off, records_size, wire_size, len(buf))
+    return CheckedTrace(int(version), meta, list(entries), p_items, po, ps, records_off, records_size, wire_size, len(buf),
+                        addend_size)
 
 
 def packed_info(path_or_bytes) -> Dict[str, Any]:
     """Sizes and the coding plan of a packed file (``python -m tachikoma_amd.trace_format info``)."""
     pf = parse_packed(_open(path_or_bytes))
     coded = sum(e.nbytes for e in pf.entries if e.coding != RAW)
-    return {"version": PACKED_VERSION, "file_bytes": pf.size, "records": len(pf.entries), "wire_bytes": pf.wire_size,
+    info = {"version": pf.version, "file_bytes": pf.size, "records": len(pf.entries), "wire_bytes": pf.wire_size,
             "coded_record_bytes": coded, "raw_record_bytes": pf.raw_size,
-            "plan": [{"name": e.name, "dtype": e.dtype, "shape": list(e.shape),
-                      "coding": "raw" if e.coding == RAW else e.coding, "diff": e.diff} for e in pf.entries]}
+            "plan": [dict({"name": e.name, "dtype": e.dtype, "shape": list(e.shape),
+                           "coding": "raw" if e.coding == RAW else e.coding, "diff": e.diff},
+                          **({"axis": e.axis} if e.coding == BIAS else {})) for e in pf.entries]}
+    if pf.version == PACKED_BIAS_VERSION:
+        info["addend_bytes"] = pf.addend_size
+    return info
 
 
 # ---------------------------------------------------------------- per-record statistics
@@ -816,6 +964,10 @@ def main(argv=None) -> int:
         q = sub.add_parser(name, help=text)
         q.add_argument("src")
         q.add_argument("dst")
+        if name == "pack":
+            q.add_argument("--bias", action="store_true",
+                           help="write version 3: bias_add records coded as the record before them plus a per-channel "
+                                "addend stored in the file")
     sub.add_parser("info", help="sizes and coding plan of a file").add_argument("src")
     sub.add_parser("stats", help="per-record statistics of the files, merged, as one JSON object").add_argument(
         "files", nargs="+")
@@ -825,11 +977,11 @@ def main(argv=None) -> int:
         return 0
     if args.cmd == "info":
         version = _header(_open(args.src))[0]
-        info = packed_info(args.src) if version == PACKED_VERSION else \
+        info = packed_info(args.src) if version in PACKED_VERSIONS else \
             {"version": version, "file_bytes": os.path.getsize(args.src), "records": len(read_trace(args.src).records)}
         print(json.dumps(info, indent=1))
         return 0
-    out = pack_trace(args.src) if args.cmd == "pack" else unpack_trace(args.src)
+    out = pack_trace(args.src, bias=args.bias) if args.cmd == "pack" else unpack_trace(args.src)
     with open(args.dst, "wb") as f:
         f.write(out)
     print(f"{args.src}: {os.path.getsize(args.src)} -> {args.dst}: {len(out)} bytes")

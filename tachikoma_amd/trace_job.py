@@ -16,7 +16,10 @@ crash at any point therefore loses at most the chunks in flight.
 With ``packed`` the chunk files are packed (version 2) trace files (trace_format.pack_trace /
 unpack_trace): same names, same manifest, same digests (the digest is of the records, not of the
 file), about half the bytes.  ``"packed"`` in a journal entry says which kind the file is, and a
-resumed job re-traces the chunks whose flag differs from its own.
+resumed job re-traces the chunks whose flag differs from its own.  With ``packed`` and ``bias``
+(``--packed --bias-coding``) they are version-3 files, which also carry the wire's bias coding and
+the addends it needs (about a seventh smaller on ResNet-50); the entry then adds ``"version": 3``,
+and entries without the field are version 2 (packed) or 1.  Every reader takes all three versions.
 
 With ``stats`` every chunk's records are also reduced on the device to per-record statistics
 (GraphModule.stats_accumulator), written beside the chunk file as ``<chunk file>.stats.json`` before
@@ -31,7 +34,7 @@ its records are copied D2H (the bench's file sink, overlapped with the next batc
 
 CLI (one process per GPU, torch.distributed.run environment; rank 0 writes the manifest)::
 
-    python -m tachikoma_amd.trace_job --model resnet50 --samples 4096 --chunk 64 --out-dir DIR [--packed]
+    python -m tachikoma_amd.trace_job --model resnet50 --samples 4096 --chunk 64 --out-dir DIR [--packed [--bias-coding]]
 
 ``--check`` traces nothing: it walks the rank's journal and verifies every chunk file against the
 engine on the device, record by record (:func:`check`, GraphModule.verify_trace), printing one JSON
@@ -134,11 +137,13 @@ class Journal:
             os.remove(self.path)
 
 
-def _valid(entry: dict, c: Chunk, verify: bool, packed: bool = False) -> bool:
+def _valid(entry: dict, c: Chunk, verify: bool, packed: bool = False, version: Optional[int] = None) -> bool:
     if (entry.get("sample_offset"), entry.get("n_samples"), entry.get("file")) != (c.sample_offset, c.n_samples,
                                                                                      os.path.basename(c.file)):
         return False
     if bool(entry.get("packed", False)) != packed:  # entries from before the flag are unpacked files
+        return False
+    if version is not None and entry.get("version", 2 if entry.get("packed") else 1) != version:
         return False
     try:
         if os.path.getsize(c.file) != entry.get("bytes"):
@@ -166,13 +171,14 @@ def run(tracer: Tracer, global_samples: int, chunk: int, out_dir: str, rank: int
     the tracer's own ``packed`` attribute, else False); it is journalled, and chunks journalled with
     the other value are traced again."""
     packed = bool(getattr(tracer, "packed", False) if packed is None else packed)
+    version = getattr(tracer, "file_version", None)  # a tracer that says which version it writes: journalled too
     os.makedirs(out_dir, exist_ok=True)
     chunks = plan_chunks(global_samples, world, rank, chunk, out_dir, stem)
     journal = Journal(journal_file(out_dir, rank, stem))
     if not resume:
         journal.reset()
     done = journal.entries() if resume else {}
-    kept = {c.index: done[c.index] for c in chunks if c.index in done and _valid(done[c.index], c, verify, packed)}
+    kept = {c.index: done[c.index] for c in chunks if c.index in done and _valid(done[c.index], c, verify, packed, version)}
     todo = [c for c in chunks if c.index not in kept]
     if log:
         log(f"rank {rank}: {len(chunks)} chunks, {len(kept)} done, {len(todo)} to trace")
@@ -187,6 +193,8 @@ def run(tracer: Tracer, global_samples: int, chunk: int, out_dir: str, rank: int
         _fsync_dir(c.file)
         e = {"chunk": c.index, "sample_offset": c.sample_offset, "n_samples": c.n_samples,
              "file": os.path.basename(c.file), "bytes": os.path.getsize(c.file), "digest": shard.hex64(digest), "packed": packed}
+        if version is not None and version >= 3:
+            e["version"] = version
         journal.append(e)
         kept[c.index] = e
 
@@ -218,15 +226,20 @@ class GraphModuleTracer:
 
     With ``packed`` the files are packed trace files: the runs are compute-only, and two packers
     (a device wire buffer and a pinned staging each) alternate, so chunk c's copy and file write
-    overlap chunk c+1's kernels; the record buffers are free as soon as the pack call returns."""
+    overlap chunk c+1's kernels; the record buffers are free as soon as the pack call returns.
+    With ``bias`` as well the files are version 3 (PackedCapture(bias=True))."""
 
     def __init__(self, build_module: Callable[[int], "object"], inputs: Callable[[int, int], "object"],
                  model: str = "graph", input_name: str = "data", rank: int = 0, world: int = 1,
-                 packed: bool = False, stats: bool = False):
+                 packed: bool = False, stats: bool = False, bias: bool = False):
+        if bias and not packed:
+            raise ValueError("GraphModuleTracer: bias coding is a coding of packed files (packed=True)")
         self.build_module = build_module
         self.inputs = inputs
         self.model, self.input_name, self.rank, self.world = model, input_name, rank, world
         self.packed = bool(packed)
+        self.bias = bool(bias)
+        self.file_version = tf.PACKED_BIAS_VERSION if self.bias else tf.PACKED_VERSION if self.packed else tf.TRACE_VERSION
         # with ``stats`` every chunk's per-record statistics are reduced on the device right after
         # its run and written beside the chunk file as <chunk file>.stats.json (stats_file)
         self.record_stats = bool(stats)
@@ -249,7 +262,7 @@ class GraphModuleTracer:
         if captures and entry[1] is None:  # a tracer that only checks files needs no trace images
             from .contrib.graph_executor import PackedCapture, TraceCapture
             m = entry[0]
-            entry[1] = ([m.packed_capture(), PackedCapture(m.module, m._meta)] if self.packed else
+            entry[1] = ([m.packed_capture(self.bias), PackedCapture(m.module, m._meta, bias=self.bias)] if self.packed else
                         [m.trace_capture(), TraceCapture(m.module, m._meta)])
         return entry
 
@@ -467,6 +480,9 @@ def main(argv=None) -> int:
     p.add_argument("--verify", action="store_true", help="re-digest resumed chunk files")
     p.add_argument("--packed", action="store_true",
                    help="write packed (version 2) chunk files: the wire coding on disk, expanded on read")
+    p.add_argument("--bias-coding", action="store_true",
+                   help="with --packed: write version-3 chunk files, whose bias_add records are coded as the record "
+                        "before them plus the bias, stored in the file")
     p.add_argument("--check", action="store_true",
                    help="trace nothing: verify every journalled chunk file against the engine, record by record, "
                         "on the device; one JSON line per chunk, exit status 1 if any chunk fails")
@@ -483,6 +499,8 @@ def main(argv=None) -> int:
     args = p.parse_args(argv)
     if args.replay and not args.check:
         p.error("--replay goes with --check")
+    if args.bias_coding and not args.packed:
+        p.error("--bias-coding goes with --packed")
     if args.stats_only and (args.check or args.stats or args.packed or args.verify):
         p.error("--stats-only writes no trace: it does not go with --check, --stats, --packed or --verify")
     import torch
@@ -503,7 +521,7 @@ def main(argv=None) -> int:
         return graph_executor.GraphModule(lib["default"](device.index))
 
     tracer = GraphModuleTracer(build_module, proto.sample_inputs, model=proto.name, input_name=proto.input_name,
-                               rank=rank, world=world, packed=args.packed, stats=args.stats)
+                               rank=rank, world=world, packed=args.packed, stats=args.stats, bias=args.bias_coding)
     log = lambda s: print(f"[trace_job] {s}", file=sys.stderr, flush=True)  # noqa: E731
     if args.stats_only:
         try:

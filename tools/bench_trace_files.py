@@ -14,7 +14,14 @@ packed chunk unpacks to the very file the unpacked job wrote and that the journa
 
 DIR holds the parent commit's ``tachikoma_amd`` package (with its library built) and ``oracle``;
 without it the parent mode is left out.  A chunk file is deleted once the next one is journalled,
-the last one after the run."""
+the last one after the run.
+
+With ``--modes`` the arms are chosen by name (default: parent, unpacked, packed): ``parent_packed`` is
+the parent tree's packed job, ``packed_bias`` this tree's ``--packed --bias-coding`` (format version
+3).  The three-arm run of the version-3 files is
+
+    python tools/bench_trace_files.py --parent-tree DIR --dir SCRATCH --modes parent_packed packed packed_bias \
+        --out profiles/packed_bias_trace_job_resnet50.json"""
 from __future__ import annotations
 
 import argparse
@@ -36,7 +43,7 @@ def child(args) -> int:
     from tachikoma_amd import relay, trace_job, zoo
     from tachikoma_amd.contrib import graph_executor
     assert os.path.dirname(os.path.dirname(os.path.abspath(trace_job.__file__))) == os.path.abspath(args.tree)
-    packed = args.child == "packed"
+    packed = args.child in ("packed", "parent_packed", "packed_bias")
     stamps, sizes = [], []
     append = trace_job.Journal.append
     import concurrent.futures
@@ -62,7 +69,8 @@ def child(args) -> int:
 
     kw = {"packed": True} if packed else {}
     tracer = trace_job.GraphModuleTracer(build_module, proto.sample_inputs, model=proto.name,
-                                         input_name=proto.input_name, **kw)
+                                         input_name=proto.input_name, **kw,
+                                         **({"bias": True} if args.child == "packed_bias" else {}))
     t0 = time.perf_counter()
     try:
         entries = trace_job.run(tracer, args.chunks * args.chunk, args.chunk, args.dir, resume=False, **kw)
@@ -77,6 +85,8 @@ def child(args) -> int:
         from tachikoma_amd import trace_format as tf
         for k in ("pack_ms", "copy_ms", "write_ms"):
             out[k] = [s[k] for s in tracer.stats[1:]]
+        with open(files[-1], "rb") as f:
+            out["file_version"] = int.from_bytes(f.read(16)[8:], "little")
         t1 = time.perf_counter()
         image = tf.unpack_trace(files[-1])
         out["unpack_ms"] = (time.perf_counter() - t1) * 1e3
@@ -101,6 +111,9 @@ def main(argv=None) -> int:
     p.add_argument("--rounds", type=int, default=3)
     p.add_argument("--dir", required=True, help="scratch directory for the chunk files (emptied after every run)")
     p.add_argument("--parent-tree", default=None, help="the parent commit's package, built")
+    p.add_argument("--modes", nargs="+", default=None,
+                   choices=["parent", "parent_packed", "unpacked", "packed", "packed_bias"],
+                   help="the arms of a round, in order (default: parent, unpacked, packed)")
     p.add_argument("--out", default=None, help="write the report (JSON) here")
     p.add_argument("--timeout", type=int, default=600, help="seconds one run may take")
     p.add_argument("--append-to", default=None,
@@ -113,7 +126,11 @@ def main(argv=None) -> int:
         return child(args)
     if args.chunks < 2:
         p.error("--chunks must be at least 2 (the first chunk is not timed)")
-    modes = ([("parent", args.parent_tree)] if args.parent_tree else []) + [("unpacked", ROOT), ("packed", ROOT)]
+    names = args.modes or ["parent", "unpacked", "packed"]
+    modes = [(m, args.parent_tree if m.startswith("parent") else ROOT) for m in names
+             if args.parent_tree or not m.startswith("parent")]
+    packed_modes = ("packed", "parent_packed", "packed_bias")
+    compared = next((m for m in names if m in packed_modes), None) if "unpacked" in names else None
     os.makedirs(args.dir, exist_ok=True)
     kept = os.path.join(args.dir, "kept_unpacked_chunk.tkt")
     st = os.statvfs(args.dir)
@@ -132,7 +149,7 @@ def main(argv=None) -> int:
             run_dir = os.path.join(args.dir, f"r{r}_{mode}")
             cmd = [sys.executable, os.path.abspath(__file__), "--child", mode, "--tree", os.path.abspath(tree),
                    "--dir", run_dir, "--model", args.model, "--chunk", str(args.chunk), "--chunks", str(args.chunks)]
-            if mode == "packed" and r == first:
+            if mode == compared and r == first:
                 cmd += ["--compare-with", kept]
             env = dict(os.environ, PYTHONPATH=os.path.abspath(tree))
             res = subprocess.run(cmd, capture_output=True, text=True, timeout=args.timeout, env=env, cwd=tree)
@@ -156,18 +173,27 @@ def main(argv=None) -> int:
         s = {"ms_per_chunk": _spread([x for run in runs for x in run["chunk_ms"]]),
              "ms_per_chunk_by_round": [_spread(run["chunk_ms"]) for run in runs],
              "bytes_per_chunk_file": _spread([x for run in runs for x in run["file_bytes"]])}
-        if mode == "packed":
+        if mode in packed_modes:
             for k in ("pack_ms", "copy_ms", "write_ms"):
                 s[k] = _spread([x for run in runs for x in run[k]])
             s["unpack_ms_one_chunk"] = _spread([run["unpack_ms"] for run in runs])
-            s["unpacks_to_the_unpacked_file"] = all(run["unpacks_to_the_unpacked_file"] for run in runs
-                                                    if "unpacks_to_the_unpacked_file" in run)
+            s["file_version"] = sorted({run["file_version"] for run in runs})
+            if any("unpacks_to_the_unpacked_file" in run for run in runs):
+                s["unpacks_to_the_unpacked_file"] = all(run["unpacks_to_the_unpacked_file"] for run in runs
+                                                        if "unpacks_to_the_unpacked_file" in run)
         summary[mode] = s
     if "unpacked" in summary and "packed" in summary:
         summary["packed_over_unpacked_bytes"] = round(summary["packed"]["bytes_per_chunk_file"]["median"] /
                                                       summary["unpacked"]["bytes_per_chunk_file"]["median"], 4)
         summary["journal_digests_equal"] = all(rd["packed"]["digests"] == rd["unpacked"]["digests"]
                                                for rd in report["rounds"])
+    have = [m for m, _ in modes if m in packed_modes]
+    if len(have) > 1:   # the packed arms agree on the records, whatever the coding
+        summary["packed_journal_digests_equal"] = all(rd[m]["digests"] == rd[have[0]]["digests"]
+                                                      for rd in report["rounds"] for m in have)
+        if "packed_bias" in summary and "packed" in summary:
+            summary["bias_over_packed_bytes"] = round(summary["packed_bias"]["bytes_per_chunk_file"]["median"] /
+                                                      summary["packed"]["bytes_per_chunk_file"]["median"], 4)
     report["summary"] = summary
     text = json.dumps(report, indent=1)
     if args.out:

@@ -16,6 +16,17 @@ process (the probe), and the compare call's wire plus record bytes per second.
 
     python tools/bench_trace_verify.py --out profiles/trace_verify_resnet50.json [--dir SCRATCH]
 
+With ``--bias`` the packed chunk is a version-3 file (the trace job's ``--packed --bias-coding``).
+With ``--kernel-times`` the tool measures the decode kernels alone instead: the chunk is written
+(``--bias`` or not), and one device run per ``--tree`` (default: this tree; a parent checkout with its
+library built may be named beside it) is taken under ``rocprofv3 --kernel-trace --stats``, each a
+profiler run of its own with that tree's copy of this tool as the program; reported are the rows of
+``wire_decode_kernel`` from the profiler's kernel statistics (calls, total, average, min, max in ns;
+a device run verifies twice, so compare mode has two calls) and the rate of wire plus record bytes
+at the compare instantiation's average.
+
+    python tools/bench_trace_verify.py --kernel-times --tree . PARENT [--bias] --out kernel_times.json
+
 The scratch directory (default: a fresh temporary one) holds about 11 GB while the tool runs and is
 removed afterwards."""
 from __future__ import annotations
@@ -55,10 +66,11 @@ def child_write(args) -> dict:
     from tachikoma_amd import trace_job
     proto, build_module = _module(args.model, args.chunk)
     out = {}
-    for packed in (True, False):
+    for packed in (True,) if args.kernel_times else (True, False):
         d = os.path.join(args.dir, "packed" if packed else "plain")
         tracer = trace_job.GraphModuleTracer(build_module, proto.sample_inputs, model=proto.name,
-                                             input_name=proto.input_name, packed=packed)
+                                             input_name=proto.input_name, packed=packed,
+                                             **({"bias": True} if packed and args.bias else {}))
         try:
             entries = trace_job.run(tracer, args.chunk, args.chunk, d, resume=False, packed=packed)
         finally:
@@ -118,6 +130,45 @@ def child_device(args) -> dict:
         gm.close()
 
 
+def kernel_times(args, packed_file: str) -> dict:
+    """One device run per tree under the profiler; the wire_decode_kernel rows of its kernel statistics."""
+    import csv
+    import glob
+    from tachikoma_amd import trace_format as tf
+    info = tf.packed_info(packed_file)
+    moved = info["wire_bytes"] + info["coded_record_bytes"]
+    out = {"file": {k: info[k] for k in ("version", "file_bytes", "wire_bytes", "coded_record_bytes")},
+           "wire_plus_record_bytes": moved, "trees": {}}
+    for i, tree in enumerate(args.tree):
+        tree = os.path.abspath(tree)
+        d = os.path.join(args.dir, f"rocprof_{i}")
+        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "run", "--", sys.executable,
+               os.path.join(tree, "tools", "bench_trace_verify.py"), "--child", "device", "--model", args.model,
+               "--chunk", str(args.chunk), "--dir", args.dir, "--packed", packed_file]
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=tree,
+                           env=dict(os.environ, PYTHONPATH=tree))
+        line = next((ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")), None)
+        if r.returncode != 0 or line is None:
+            sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:])
+            raise SystemExit(f"{tree}: the profiled run failed ({r.returncode})")
+        rows = []
+        for path in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
+            with open(path, newline="") as f:
+                rows += [row for row in csv.DictReader(f) if "wire_decode_kernel" in row.get("Name", "")]
+        if not rows:
+            raise SystemExit(f"{tree}: the profiler's kernel statistics name no wire_decode_kernel (looked under {d})")
+        res = json.loads(line[7:])
+        entry = {"ok": res["ok"] and res["second"]["ok"], "kernels": rows}
+        for row in rows:   # compare mode is the first template argument 1
+            name = row["Name"].replace(" ", "")
+            if "wire_decode_kernel<1" in name or "wire_decode_kernel<(int)1" in name:
+                avg = float(row["AverageNs"])
+                entry["compare_avg_ms"] = avg / 1e6
+                entry["compare_TBps"] = moved / avg / 1e3
+        out["trees"][tree] = entry
+    return out
+
+
 def _spread(xs):
     return {"median": round(statistics.median(xs), 2), "min": round(min(xs), 2), "max": round(max(xs), 2)}
 
@@ -129,6 +180,10 @@ def main() -> int:
     p.add_argument("--rounds", type=int, default=3)
     p.add_argument("--dir", default=None)
     p.add_argument("--out", default=None)
+    p.add_argument("--bias", action="store_true", help="the packed chunk is a version-3 file (bias coding)")
+    p.add_argument("--kernel-times", action="store_true",
+                   help="profile the decode kernels alone (rocprofv3 --kernel-trace --stats, one run per --tree)")
+    p.add_argument("--tree", nargs="+", default=[ROOT], help="with --kernel-times: the trees to run, each with its library built")
     p.add_argument("--child", choices=["write", "host", "device"], default=None)
     p.add_argument("--packed", default=None)
     p.add_argument("--plain", default=None)
@@ -143,7 +198,8 @@ def main() -> int:
 
     def run(child, *extra):
         cmd = [sys.executable, os.path.abspath(__file__), "--child", child, "--model", args.model, "--chunk",
-               str(args.chunk), "--dir", args.dir, *extra]
+               str(args.chunk), "--dir", args.dir, *(["--bias"] if args.bias else []),
+               *(["--kernel-times"] if args.kernel_times else []), *extra]
         t0 = time.perf_counter()
         r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, check=True)
         line = next(ln for ln in r.stdout.splitlines() if ln.startswith("RESULT "))
@@ -152,6 +208,13 @@ def main() -> int:
 
     try:
         files = run("write")
+        if args.kernel_times:
+            out = kernel_times(args, files["packed"]["file"])
+            if args.out:
+                with open(args.out, "w") as f:
+                    f.write(json.dumps(out, indent=1) + "\n")
+            print(json.dumps({t: {k: v for k, v in e.items() if k != "kernels"} for t, e in out["trees"].items()}))
+            return 0
         both = ("--packed", files["packed"]["file"], "--plain", files["plain"]["file"])
         rounds = []
         for _ in range(args.rounds):
