@@ -119,12 +119,11 @@ int chunk_wire_tables(const std::vector<size_t>& coded, const int32_t* addend_de
     const int kind = wrecs[sr.rec].kind;
     const WireSegAddr dev = wire_seg_addr(sr, kind, r.src, pv ? pv->src : nullptr);
     const WireSegAddr img = wire_seg_addr(sr, kind, r.host, pv ? pv->host : nullptr);
-    plan->wire_segs.push_back({dev.at, dev.prev, sr.n, kind});
-    wc->segs.push_back({img.at, img.prev, sr.n, kind});
-    if (r.bias) {  // each side is handed its own copy of the plan's snapshot
-      wire_seg_bias(&plan->wire_segs.back(), addend_dev + r.addend_at, r.plane, r.channels, sr.e0);
-      wire_seg_bias(&wc->segs.back(), addend_host + r.addend_at, r.plane, r.channels, sr.e0);
-    }
+    auto bias = [&](const int32_t* snapshot) {  // each side is handed its own copy of the plan's snapshot
+      return wire_seg_bias(r.bias ? snapshot + r.addend_at : nullptr, r.plane, r.channels, sr.e0);
+    };
+    plan->wire_segs.push_back({dev.at, dev.prev, sr.n, kind, bias(addend_dev)});
+    wc->segs.push_back({img.at, img.prev, sr.n, kind, bias(addend_host)});
   }
   for (size_t q : coded) wc->coded_bytes += recs[q].bytes;
   return TK_OK;

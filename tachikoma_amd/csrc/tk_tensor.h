@@ -13,6 +13,8 @@ namespace tk {
 
 // ---------------------------------------------------------------- errors
 void set_error(const std::string& msg);
+// under the name of the entry point that fails
+inline void set_error(const char* who, const std::string& text) { set_error(std::string(who) + ": " + text); }
 
 // ---------------------------------------------------------------- tensors
 inline int64_t numel(const tk_tensor* t) {

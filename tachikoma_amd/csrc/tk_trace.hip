@@ -174,20 +174,20 @@ int pack_records_impl(const PackRec* table, int nrec, int64_t blocks, void* mirr
 // The channel is always one of the addend's, so the walk may run past the record's end.
 __device__ __forceinline__ uint32_t wire_byte(const uint32_t* w, int j) { return (w[j >> 2] >> (8 * (j & 3))) & 0xFFu; }
 
-__device__ __forceinline__ void wire_sub_addend(uint32_t* x, const WireSegDev& sg, int e0) {
-  const uint32_t plane = (uint32_t)sg.plane, channels = (uint32_t)sg.channels;
-  const uint32_t t = (uint32_t)sg.r0 + (uint32_t)e0;
+__device__ __forceinline__ void wire_sub_addend(uint32_t* x, const WireBias& wb, int e0) {
+  const uint32_t plane = (uint32_t)wb.plane, channels = (uint32_t)wb.channels;
+  const uint32_t t = (uint32_t)wb.r0 + (uint32_t)e0;
   const uint32_t q = t / plane;
   uint32_t r = t - q * plane;
-  uint32_t c = ((uint32_t)sg.c0 + q) % channels;
-  uint32_t a = (uint32_t)sg.addend[c];
+  uint32_t c = ((uint32_t)wb.c0 + q) % channels;
+  uint32_t a = (uint32_t)wb.addend[c];
 #pragma unroll
   for (int j = 0; j < 16; ++j) {
     x[j] -= a;
     if (++r == plane) {
       r = 0;
       c = c + 1 == channels ? 0 : c + 1;
-      a = (uint32_t)sg.addend[c];
+      a = (uint32_t)wb.addend[c];
     }
   }
 }
@@ -287,7 +287,7 @@ __global__ __launch_bounds__(256) void wire_encode_kernel(const WireSegDev* __re
                 v[p][4 * q + 3] -= (uint32_t)a.w;
           }
         }
-        if (sg.addend) wire_sub_addend(v[p], sg, e0);
+        if (sg.bias.addend) wire_sub_addend(v[p], sg.bias, e0);
 #pragma unroll
         for (int j = 0; j < 16; ++j) mn = min(mn, (int32_t)v[p][j]), mx = max(mx, (int32_t)v[p][j]);
       } else {
@@ -301,7 +301,7 @@ __global__ __launch_bounds__(256) void wire_encode_kernel(const WireSegDev* __re
           v[p][j] = x;
         }
         // (the walk also passes over the elements past the record's end: they are never stored)
-        if (sg.addend && e0 < n) wire_sub_addend(v[p], sg, e0);
+        if (sg.bias.addend && e0 < n) wire_sub_addend(v[p], sg.bias, e0);
 #pragma unroll
         for (int j = 0; j < 16; ++j)
           if (e0 + j < n) mn = min(mn, (int32_t)v[p][j]), mx = max(mx, (int32_t)v[p][j]);
@@ -564,7 +564,7 @@ enum { kWireStore = 0, kWireCompare = 1 };
 template <int kMode, bool kBias>
 __global__ __launch_bounds__(256) void wire_decode_kernel(const WireUnitDev* __restrict__ units,
                                                           const WireSegOut* __restrict__ segs,
-                                                          const WireSegBias* __restrict__ bias,
+                                                          const WireBias* __restrict__ bias,
                                                           const uint32_t* __restrict__ table,
                                                           const uint8_t* __restrict__ payload, int64_t payload_bytes,
                                                           tk_wire_mismatch* report, uint32_t* status) {
@@ -622,7 +622,7 @@ __global__ __launch_bounds__(256) void wire_decode_kernel(const WireUnitDev* __r
       return;
     }
     const WireSegOut so = segs[si];
-    WireSegBias sb{};
+    WireBias sb{};
     if constexpr (kBias) sb = bias[si];
     const uint64_t e_seg = (uint64_t)un.e0;
     uint32_t mis = 0, first = 0xFFFFFFFFu;  // the first differing element, counted within the segment
@@ -795,11 +795,11 @@ static void wire_decode_launch(const void* units, int64_t n_units, const void* s
                                int64_t table, int64_t wire_bytes, tk_wire_mismatch* report, uint32_t* status,
                                hipStream_t s) {
   hipLaunchKernelGGL((wire_decode_kernel<kMode, kBias>), dim3((unsigned)n_units), dim3(256), 0, s,
-                     (const WireUnitDev*)units, (const WireSegOut*)segs, (const WireSegBias*)bias, (const uint32_t*)wire,
+                     (const WireUnitDev*)units, (const WireSegOut*)segs, (const WireBias*)bias, (const uint32_t*)wire,
                      (const uint8_t*)wire + table, wire_bytes - table, report, status);
 }
 
-// `bias` (device, a WireSegBias per segment) selects the instantiations that know addends; null: none.
+// `bias` (device, a WireBias per segment) selects the instantiations that know addends; null: none.
 static int wire_unpack_impl(const void* units, int64_t n_units, const void* segs, const void* bias, const void* wire,
                             int64_t n_seg, int64_t wire_bytes, int mode, tk_wire_mismatch* report, int n_report,
                             uint32_t* status, hipStream_t s) {
@@ -929,9 +929,7 @@ std::vector<tk::WireSegDev> source_segs(const tk::WirePlan& plan, const tk_wire_
   for (const tk::WireSegRef& r : plan.segs) {
     const int kind = tk::wire_seg_kind(recs[r.rec].kind);
     const tk::WireSegAddr a = tk::wire_seg_addr(r, kind, src[r.rec], recs[r.rec].diff ? src[r.rec - 1] : nullptr);
-    segs.push_back({a.at, a.prev, r.n, kind});
-    if (const tk_wire_addend* ad = tk::wire_addend_of(recs, addends, r.rec))
-      tk::wire_seg_bias(&segs.back(), ad->addend, ad->plane, ad->channels, r.e0);
+    segs.push_back({a.at, a.prev, r.n, kind, tk::wire_seg_bias(recs, addends, r.rec, r.e0)});
   }
   return segs;
 }
@@ -1017,11 +1015,11 @@ int64_t tk_wire_pack_device(const tk_wire_record* recs, int n_recs, const void* 
 
 int64_t tk_wire_pack_device_bias(const tk_wire_record* recs, const tk_wire_addend* addends, int n_recs,
                                  const void* const* src, void* wire, int64_t wire_cap, void* stream) {
-  const std::string who = addends ? "tk_wire_pack_device_bias" : "tk_wire_pack_device";  // errors name the entry point called
+  const char* who = addends ? "tk_wire_pack_device_bias" : "tk_wire_pack_device";  // errors name the entry point called
   tk::WirePlan plan;
-  if (const int rc = tk::wire_plan(recs, n_recs, -1, who.c_str(), &plan, addends)) return rc;
+  if (const int rc = tk::wire_plan(recs, n_recs, -1, who, &plan, addends)) return rc;
   if (!src || !wire || ((uintptr_t)wire & 63) != 0 || wire_cap < plan.bound) {
-    tk::set_error(who + ": the wire buffer is not 64-byte aligned or smaller than tk_wire_bound");
+    tk::set_error(who, "the wire buffer is not 64-byte aligned or smaller than tk_wire_bound");
     return TK_ERR_INVALID_ARG;
   }
   const std::vector<tk::WireSegDev> segs = source_segs(plan, recs, src, addends);
@@ -1043,18 +1041,18 @@ int64_t tk_wire_pack_device_bias(const tk_wire_record* recs, const tk_wire_adden
   TK_HIP(hipMemcpyAsync(&total, scan + words - 1, sizeof(total), hipMemcpyDeviceToHost, s));
   TK_HIP(hipStreamSynchronize(s));
   if (total > 0xFFFFFFF0ull) {
-    tk::set_error(who + ": the packed records do not fit the format's 32-bit segment starts");
+    tk::set_error(who, "the packed records do not fit the format's 32-bit segment starts");
     return TK_ERR_UNSUPPORTED;
   }
   const int64_t used = table + 64 * (int64_t)total;
   if (used > plan.bound) {
-    tk::set_error(who + ": the segment sizes exceed tk_wire_bound");
+    tk::set_error(who, "the segment sizes exceed tk_wire_bound");
     return TK_ERR_HIP;
   }
   rc = tk::wire_pack_place_impl(dev_segs, n_seg, wire, used, s);
   if (rc != TK_OK) return rc;
   if (hipStreamSynchronize(s) != hipSuccess) {
-    tk::set_error(who + ": the place kernel failed");
+    tk::set_error(who, "the place kernel failed");
     return TK_ERR_HIP;
   }
   return used;
@@ -1070,25 +1068,25 @@ int tk_wire_unpack_device(const tk_wire_record* recs, int n_recs, const void* wi
 int tk_wire_unpack_device_bias(const tk_wire_record* recs, const tk_wire_addend* addends, int n_recs, const void* wire,
                                int64_t wire_bytes, void* const* dst, int mode, tk_wire_mismatch* report,
                                void* stream) {
-  const std::string who = addends ? "tk_wire_unpack_device_bias" : "tk_wire_unpack_device";  // errors name the entry point called
+  const char* who = addends ? "tk_wire_unpack_device_bias" : "tk_wire_unpack_device";  // errors name the entry point called
   tk::WirePlan plan;
-  if (const int rc = tk::wire_plan(recs, n_recs, -1, who.c_str(), &plan, addends)) return rc;
+  if (const int rc = tk::wire_plan(recs, n_recs, -1, who, &plan, addends)) return rc;
   const bool compare = mode == TK_WIRE_UNPACK_COMPARE;
   if (!wire || !dst || ((uintptr_t)wire & 63) != 0 || (mode != TK_WIRE_UNPACK_STORE && !compare) ||
       (compare && !report)) {
-    tk::set_error(who + ": null argument, unknown mode or a wire buffer that is not 64-byte aligned");
+    tk::set_error(who, "null argument, unknown mode or a wire buffer that is not 64-byte aligned");
     return TK_ERR_INVALID_ARG;
   }
   for (int i = 0; i < n_recs; ++i)
     if (tk::wire_seg_kind(recs[i].kind) == tk::kWireI32 && ((uintptr_t)dst[i] & 3) != 0) {
-      tk::set_error(who + ": the buffer of int32 record " + std::to_string(i) + " is not 4-byte aligned");
+      tk::set_error(who, "the buffer of int32 record " + std::to_string(i) + " is not 4-byte aligned");
       return TK_ERR_INVALID_ARG;
     }
   const std::vector<tk::WireSegRef>& refs = plan.segs;
   const std::vector<tk::WireUnit>& units = plan.units;
   const int64_t n_seg = (int64_t)refs.size(), n_units = (int64_t)units.size();
   if (wire_bytes < tk::wire_table_bytes(n_seg)) {
-    tk::set_error(who + ": the segment table does not lie inside the wire buffer");
+    tk::set_error(who, "the segment table does not lie inside the wire buffer");
     return TK_ERR_INVALID_ARG;
   }
   std::vector<tk::WireSegOut> segs(refs.size());
@@ -1100,16 +1098,16 @@ int tk_wire_unpack_device_bias(const tk_wire_record* recs, const tk_wire_addend*
     udev[u] = {units[u].first, units[u].stride, units[u].count, r.n, tk::wire_seg_kind(recs[r.rec].kind), 0, r.e0};
   }
   // the bias table (and with it the instantiations that read one) only where a record has an addend
-  std::vector<tk::WireSegBias> bias;
+  std::vector<tk::WireBias> bias;
   for (size_t i = 0; i < refs.size(); ++i)
-    if (const tk_wire_addend* ad = tk::wire_addend_of(recs, addends, refs[i].rec)) {
+    if (tk::wire_addend_of(recs, addends, refs[i].rec)) {
       if (bias.empty()) bias.resize(refs.size());
-      tk::wire_seg_bias(&bias[i], ad->addend, ad->plane, ad->channels, refs[i].e0);
+      bias[i] = tk::wire_seg_bias(recs, addends, refs[i].rec, refs[i].e0);
     }
   const int64_t seg_bytes = tk::wire_align(n_seg * (int64_t)sizeof(tk::WireSegOut), 64);
   const int64_t unit_bytes = tk::wire_align(n_units * (int64_t)sizeof(tk::WireUnitDev), 64);
   const int64_t rep_bytes = tk::wire_align((int64_t)n_recs * (int64_t)sizeof(tk_wire_mismatch), 64);
-  const int64_t bias_bytes = tk::wire_align((int64_t)bias.size() * (int64_t)sizeof(tk::WireSegBias), 64);
+  const int64_t bias_bytes = tk::wire_align((int64_t)bias.size() * (int64_t)sizeof(tk::WireBias), 64);
   hipStream_t s = tk::as_stream(stream);
   std::lock_guard<std::mutex> lock(g_unpack_scratch.mu);
   char* dev = nullptr;
@@ -1117,7 +1115,7 @@ int tk_wire_unpack_device_bias(const tk_wire_record* recs, const tk_wire_addend*
   if (rc != TK_OK) return rc;
   char* dev_bias = bias.empty() ? nullptr : dev + seg_bytes + unit_bytes + rep_bytes + 64;
   if (dev_bias)
-    TK_HIP(hipMemcpyAsync(dev_bias, bias.data(), bias.size() * sizeof(tk::WireSegBias), hipMemcpyHostToDevice, s));
+    TK_HIP(hipMemcpyAsync(dev_bias, bias.data(), bias.size() * sizeof(tk::WireBias), hipMemcpyHostToDevice, s));
   tk_wire_mismatch* rep = (tk_wire_mismatch*)(dev + seg_bytes + unit_bytes);
   uint32_t* status = (uint32_t*)(dev + seg_bytes + unit_bytes + rep_bytes);
   TK_HIP(hipMemcpyAsync(dev, segs.data(), segs.size() * sizeof(tk::WireSegOut), hipMemcpyHostToDevice, s));
@@ -1129,11 +1127,11 @@ int tk_wire_unpack_device_bias(const tk_wire_record* recs, const tk_wire_addend*
   if (compare) TK_HIP(hipMemcpyAsync(report, rep, (size_t)n_recs * sizeof(tk_wire_mismatch), hipMemcpyDeviceToHost, s));
   TK_HIP(hipMemcpyAsync(&bad, status, sizeof(bad), hipMemcpyDeviceToHost, s));
   if (hipStreamSynchronize(s) != hipSuccess) {
-    tk::set_error(who + ": the decode kernel failed");
+    tk::set_error(who, "the decode kernel failed");
     return TK_ERR_HIP;
   }
   if (bad) {
-    tk::set_error(who + ": a segment does not lie inside the wire buffer or states a width its kind "
+    tk::set_error(who, "a segment does not lie inside the wire buffer or states a width its kind "
                   "does not have (was the buffer checked with tk_wire_check?)");
     return TK_ERR_INVALID_ARG;
   }

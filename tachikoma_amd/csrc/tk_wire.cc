@@ -200,8 +200,7 @@ void widen_w(int w, char* dst, const char* prev, const uint8_t* p, int cnt, uint
 struct BiasWalk {
   const int32_t* addend;
   int32_t plane, channels, c, r;
-  template <typename Seg>
-  explicit BiasWalk(const Seg& s) : addend(s.addend), plane(s.plane), channels(s.channels), c(s.c0), r(s.r0) {}
+  explicit BiasWalk(const WireBias& b) : addend(b.addend), plane(b.plane), channels(b.channels), c(b.c0), r(b.r0) {}
   int run(int left) const { return std::min(left, plane - r); }  // elements up to the plane's end
   uint32_t value() const { return (uint32_t)addend[c]; }
   void advance(int k) {  // k <= run()
@@ -274,7 +273,7 @@ int64_t decode_seg(const WireJob& j, int64_t i, const char* payload, int64_t pay
     }
     return wire_align(len, 64);
   }
-  BiasWalk walk(sg);
+  BiasWalk walk(sg.bias);
   for (int b = 0; b < nb; ++b) {
     const int cnt = std::min(kWireBlock, sg.n - b * kWireBlock);
     const int w = widths[b];
@@ -282,7 +281,7 @@ int64_t decode_seg(const WireJob& j, int64_t i, const char* payload, int64_t pay
     std::memcpy(&base, p + 4 * b, 4);
     char* dst = sg.dst + 4 * (int64_t)b * kWireBlock;
     const char* prev = sg.prev ? sg.prev + 4 * (int64_t)b * kWireBlock : nullptr;
-    if (sg.addend && prev) {
+    if (sg.bias.addend && prev) {
       if (walk.run(cnt) == cnt) {  // one channel: the block's constant is its base plus that addend
         widen_w<true>(w, dst, prev, q, cnt, (uint32_t)base + walk.value());
         walk.advance(cnt);
@@ -447,9 +446,7 @@ int64_t tk_wire_encode_host_bias(const tk_wire_record* recs, const tk_wire_adden
                           recs[s.rec].diff ? (const char*)image + recs[s.rec - 1].offset : nullptr);
     const uint32_t start = (uint32_t)(cursor / 64);
     std::memcpy((char*)wire + 4 * i, &start, 4);
-    tk::WireSegHost bias{};
-    if (const tk_wire_addend* ad = tk::wire_addend_of(recs, addends, s.rec))
-      tk::wire_seg_bias(&bias, ad->addend, ad->plane, ad->channels, s.e0);
+    const tk::WireBias bias = tk::wire_seg_bias(recs, addends, s.rec, s.e0);
     tk::BiasWalk walk(bias);
     const int64_t len = kind == tk::kWireI32
                             ? tk::encode_seg(a.at, a.prev, s.n, payload + cursor, bias.addend ? &walk : nullptr)
@@ -480,9 +477,7 @@ int tk_wire_decode_bias(const tk_wire_record* recs, const tk_wire_addend* addend
     const tk::WireSegAddr a =
         tk::wire_seg_addr(s, recs[s.rec].kind, (char*)image + recs[s.rec].offset,
                           recs[s.rec].diff ? (const char*)image + recs[s.rec - 1].offset : nullptr);
-    segs[i] = {a.at, a.prev, s.n, tk::wire_seg_kind(recs[s.rec].kind)};
-    if (const tk_wire_addend* ad = tk::wire_addend_of(recs, addends, s.rec))
-      tk::wire_seg_bias(&segs[i], ad->addend, ad->plane, ad->channels, s.e0);
+    segs[i] = {a.at, a.prev, s.n, tk::wire_seg_kind(recs[s.rec].kind), tk::wire_seg_bias(recs, addends, s.rec, s.e0)};
   }
   tk::WireJob job{(const char*)wire, wire_bytes, segs.data(), (int64_t)segs.size(),
                   p.units.data(), (int64_t)p.units.size()};
@@ -500,13 +495,13 @@ int tk_wire_check(const tk_wire_record* recs, int n_recs, const void* wire, int6
 // The addends are looked at as wire_plan looks at them (pointer, plane, channels): no value is read.
 int tk_wire_check_bias(const tk_wire_record* recs, const tk_wire_addend* addends, int n_recs, const void* wire,
                        int64_t wire_bytes) {
-  const std::string who = addends ? "tk_wire_check_bias" : "tk_wire_check";  // errors name the entry point called
+  const char* who = addends ? "tk_wire_check_bias" : "tk_wire_check";  // errors name the entry point called
   tk::WirePlan p;
-  if (const int rc = tk::wire_plan(recs, n_recs, -1, who.c_str(), &p, addends)) return rc;
+  if (const int rc = tk::wire_plan(recs, n_recs, -1, who, &p, addends)) return rc;
   const int64_t n_seg = (int64_t)p.segs.size();
   const int64_t table = tk::wire_table_bytes(n_seg);
   if (!wire || wire_bytes < table) {
-    tk::set_error(who + ": the segment table does not lie inside the wire buffer");
+    tk::set_error(who, "the segment table does not lie inside the wire buffer");
     return TK_ERR_INVALID_ARG;
   }
   const char* payload = (const char*)wire + table;
@@ -515,8 +510,8 @@ int tk_wire_check_bias(const tk_wire_record* recs, const tk_wire_addend* addends
     std::memcpy(&start, (const char*)wire + 4 * i, 4);
     if (tk::wire_seg_extent(tk::wire_seg_kind(recs[p.segs[i].rec].kind), p.segs[i].n, start, payload,
                             wire_bytes - table) < 0) {
-      tk::set_error(who + ": segment " + std::to_string(i) + " (record " + std::to_string(p.segs[i].rec) +
-                    ") does not lie inside the wire buffer or states a width its kind does not have");
+      tk::set_error(who, "segment " + std::to_string(i) + " (record " + std::to_string(p.segs[i].rec) +
+                             ") does not lie inside the wire buffer or states a width its kind does not have");
       return TK_ERR_INVALID_ARG;
     }
   }

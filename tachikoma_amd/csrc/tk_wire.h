@@ -75,6 +75,18 @@ struct WireSegPos { int32_t c0, r0; };
 inline WireSegPos wire_seg_pos(int64_t e0, int32_t plane, int32_t channels) {
   return {(int32_t)((e0 / plane) % channels), (int32_t)(e0 % plane)};
 }
+// The bias coding of a segment (WireSegDev, WireSegHost; the device decoder's table parallel to WireSegOut).
+struct WireBias {
+  const int32_t* addend = nullptr;  // `channels` values whoever reads the segment can read; null: no addend
+  int32_t plane = 0, channels = 0;
+  int32_t c0 = 0, r0 = 0;           // wire_seg_pos of the segment's first element
+};
+// of a segment that starts at element e0 of a record coded with `addend` (null: none)
+inline WireBias wire_seg_bias(const int32_t* addend, int32_t plane, int32_t channels, int64_t e0) {
+  if (!addend) return {};
+  const WireSegPos at = wire_seg_pos(e0, plane, channels);
+  return {addend, plane, channels, at.c0, at.r0};
+}
 
 // device encoder's view of a segment
 struct WireSegDev {
@@ -82,21 +94,13 @@ struct WireSegDev {
   const void* prev;  // differenced against / clamp-predicted from (device), or null
   int32_t n;
   int32_t kind;
-  const int32_t* addend = nullptr;  // bias coding (device, `channels` values), or null
-  int32_t plane = 0, channels = 0;
-  int32_t c0 = 0, r0 = 0;           // wire_seg_pos of the segment's first element
+  WireBias bias;     // addend on the device
 };
 // device decoder's view (tk_wire_unpack_device): a segment's destination, and a decode unit
 struct WireSegOut {
   void* dst;  // the segment's first element in the record's buffer (device), or null
   int32_t rec;
   int32_t pad;
-};
-// the bias coding of a segment, in a table parallel to WireSegOut (tk_wire_unpack_device_bias)
-struct WireSegBias {
-  const int32_t* addend = nullptr;  // device, `channels` values; null: the segment has no addend
-  int32_t plane = 0, channels = 0;
-  int32_t c0 = 0, r0 = 0;           // wire_seg_pos of the segment's first element
 };
 struct WireUnitDev {
   int32_t first, stride, count;  // segments first, first + stride, ...
@@ -119,10 +123,10 @@ struct WireSegHost {
   const char* prev;  // differenced against / clamp-predicted from (image bytes already present), or null
   int32_t n;
   int32_t kind;
-  const int32_t* addend = nullptr;  // bias coding (host, `channels` values), or null
-  int32_t plane = 0, channels = 0;
-  int32_t c0 = 0, r0 = 0;           // wire_seg_pos of the segment's first element
+  WireBias bias;     // addend on the host
 };
+// (the tables uploaded to the device keep their sizes)
+static_assert(sizeof(WireBias) == 24 && sizeof(WireSegDev) == 48 && sizeof(WireSegHost) == 48, "wire segment layout");
 // One decoder work item: segments first, first + stride, ... (`count` of them), decoded in this
 // order by one thread: the same segment of a chain of records differenced against each other.
 struct WireUnit {
@@ -165,13 +169,10 @@ inline WireSegAddr wire_seg_addr(const WireSegRef& s, int kind, const void* base
   return {base ? (char*)base + b0 : nullptr, prev_base ? (const char*)prev_base + b0 : nullptr};
 }
 
-// The bias coding of a segment (WireSegDev / WireSegHost) that starts at element e0 of a record
-// coded with `addend` (null: none), which whoever reads the segment's sources can read.
-template <typename Seg>
-inline void wire_seg_bias(Seg* s, const int32_t* addend, int32_t plane, int32_t channels, int64_t e0) {
-  if (!addend) return;
-  const WireSegPos at = wire_seg_pos(e0, plane, channels);
-  s->addend = addend, s->plane = plane, s->channels = channels, s->c0 = at.c0, s->r0 = at.r0;
+// The same for a record of an entry point's list: record i's coding where it has an addend, else none.
+inline WireBias wire_seg_bias(const tk_wire_record* recs, const tk_wire_addend* addends, int i, int64_t e0) {
+  const tk_wire_addend* ad = wire_addend_of(recs, addends, i);
+  return ad ? wire_seg_bias(ad->addend, ad->plane, ad->channels, e0) : WireBias{};
 }
 
 // Unrounded length of a segment of n elements of `kind` placed at table entry `start`, from the

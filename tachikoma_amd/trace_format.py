@@ -474,9 +474,9 @@ def _parse_plan(mv, off: int, end: int, n: int, version: int = PACKED_VERSION) -
     return entries
 
 
-def _wire_records(entries: Sequence[PackedEntry], offsets: Sequence[int]):
+def _wire_records(entries: Sequence[PackedEntry], offsets: Optional[Sequence[int]] = None):
     """tk_wire_record array of the coded entries (offsets: each entry's payload offset in the image)."""
-    coded = [(e, o) for e, o in zip(entries, offsets) if e.coding != RAW]
+    coded = [(e, o) for e, o in zip(entries, offsets or [0] * len(entries)) if e.coding != RAW]
     arr = (_lib.tk_wire_record * max(1, len(coded)))()
     for i, (e, o) in enumerate(coded):
         arr[i].offset, arr[i].n_elems, arr[i].diff, arr[i].kind = int(o), _n_elems(e.shape), e.diff, e.coding
@@ -494,16 +494,68 @@ def _wire_addends(entries: Sequence[PackedEntry], base: int):
     return arr
 
 
-def packed_section_head(entries: Sequence[PackedEntry], wire_size: int, addend_size: Optional[int] = None) -> bytes:
-    """The records section of a packed file up to the wire (version 2) or up to the addends part
-    (version 3: ``addend_size`` given): section header, plan, pad to 8."""
-    plan = _plan_bytes(entries)
-    raw_size = sum(e.raw_size for e in entries)
-    if addend_size is None:
-        head = _SECTION.pack(PACK_MAGIC, len(entries), len(plan), wire_size, raw_size) + plan
-    else:
-        head = _SECTION3.pack(PACK_MAGIC, len(entries), len(plan), wire_size, raw_size, addend_size) + plan
-    return head + b"\0" * (_align(len(head), 8) - len(head))
+def wire_call(name: str, recs, addends, n: int, *rest, reader: bool = False) -> int:
+    """The wire entry point ``name`` over ``recs`` (a packed file of version 2: ``addends`` None), or
+    its twin that takes addends, ``name + "_bias"`` (version 3, with or without a bias-coded record).
+    Returns what it returns; a failure is raised under the name of the entry point called
+    (TachikomaError; for a ``reader`` of packed files the ValueError of a file that does not hold)."""
+    lib = _lib.load()
+    name, head = (name, (recs, n)) if addends is None else (name + "_bias", (recs, addends, n))
+    rc = getattr(lib, name)(*head, *rest)
+    if rc < 0 and reader:
+        raise ValueError("packed trace: " + lib.tk_last_error().decode(errors="replace"))
+    if rc < 0:
+        _lib.check(int(rc), name)
+    return int(rc)
+
+
+@dataclass
+class PackedPlan:
+    """The records section of a packed file, from its entries and its version (2, or 3: a section
+    header with ``addend_size`` and an addends part in front of the wire, whether or not an entry
+    is bias-coded):  head | addends | wire | raw."""
+    entries: List[PackedEntry]
+    version: int = PACKED_VERSION
+
+    def __post_init__(self):
+        if self.version not in PACKED_VERSIONS:
+            raise ValueError(f"not a packed trace version: {self.version}")
+        self.bias = self.version == PACKED_BIAS_VERSION
+        self.section = _SECTION3 if self.bias else _SECTION
+        self.addend_size = addend_bytes(self.entries) if self.bias else 0
+        self.raw_size = sum(e.raw_size for e in self.entries)
+
+    def head(self, wire_size: int) -> bytes:
+        """The section up to the addends part: section header, plan, pad to 8."""
+        plan = _plan_bytes(self.entries)
+        sizes = (wire_size, self.raw_size) + ((self.addend_size,) if self.bias else ())
+        head = self.section.pack(PACK_MAGIC, len(self.entries), len(plan), *sizes) + plan
+        return head + b"\0" * (_align(len(head), 8) - len(head))
+
+    def size(self, wire_size: int) -> int:
+        """Bytes of the whole section with a wire of ``wire_size`` (or of ``wire_bound()``)."""
+        return len(self.head(wire_size)) + self.addend_size + wire_size + self.raw_size
+
+    def wire_records(self, offsets: Optional[Sequence[int]] = None):
+        """(tk_wire_record array, count) of the coded entries."""
+        return _wire_records(self.entries, offsets)
+
+    def wire_addends(self, base: int):
+        """tk_wire_addend array for an addends part at address ``base``; None for version 2 (see wire_call)."""
+        return _wire_addends(self.entries, base) if self.bias else None
+
+    def wire_bound(self) -> int:
+        """tk_wire_bound of the coded entries: the wire's size with every block raw (0: none coded)."""
+        recs, n = self.wire_records()
+        bound = int(_lib.load().tk_wire_bound(recs, n)) if n else 0
+        if bound < 0:
+            _lib.check(bound, "tk_wire_bound")
+        return bound
+
+
+def packed_section_head(entries: Sequence[PackedEntry], wire_size: int, version: int = PACKED_VERSION) -> bytes:
+    """PackedPlan.head of the entries: the records section up to the wire or the addends part."""
+    return PackedPlan(list(entries), version).head(wire_size)
 
 
 def _ptr(buf) -> Tuple[int, np.ndarray]:
@@ -526,38 +578,28 @@ def pack_trace(path_or_bytes, bias: bool = False) -> bytes:
         raise ValueError(f"pack_trace wants a version-{TRACE_VERSION} trace, not version {version}")
     if not 56 + jl <= po <= po + ps <= ro <= ro + rs <= len(buf):
         raise ValueError("truncated trace file")
-    lib = _lib.load()
     records = parse_ndarray_list(buf, ro, rs)
     base, keep = _ptr(buf)
     items = [(k, v.shape, str(v.dtype)) for k, v in records.items()]
     offsets = [(v.ctypes.data - base) if v.size else ro for v in records.values()]
     axes, values = bias_axes_of_data(records) if bias else ({}, {})
-    entries = packed_entries(items, bias_axes=axes)
-    addends = np.zeros(addend_bytes(entries) // 4, "<i4")
+    plan = PackedPlan(packed_entries(items, bias_axes=axes), PACKED_BIAS_VERSION if bias else PACKED_VERSION)
+    entries = plan.entries
+    addends = np.zeros(plan.addend_size // 4, "<i4")
     for i, v in values.items():
         addends[entries[i].addend_off // 4:entries[i].addend_off // 4 + v.size] = v
-    recs, n = _wire_records(entries, offsets)
+    recs, n = plan.wire_records(offsets)
     wire = b""
     if n:
-        bound = lib.tk_wire_bound(recs, n)
-        if bound < 0:
-            _lib.check(int(bound), "tk_wire_bound")
+        bound = plan.wire_bound()
         out = np.empty(bound, np.uint8)
-        if bias:
-            used = lib.tk_wire_encode_host_bias(recs, _wire_addends(entries, addends.ctypes.data), n, ctypes.c_void_p(base),
-                                                len(buf), ctypes.c_void_p(out.ctypes.data), bound)
-        else:
-            used = lib.tk_wire_encode_host(recs, n, ctypes.c_void_p(base), len(buf), ctypes.c_void_p(out.ctypes.data),
-                                           bound)
-        if used < 0:
-            _lib.check(int(used), "tk_wire_encode_host")
+        used = wire_call("tk_wire_encode_host", recs, plan.wire_addends(addends.ctypes.data), n, ctypes.c_void_p(base),
+                         len(buf), ctypes.c_void_p(out.ctypes.data), bound)
         wire = out[:used].tobytes()
-    head = packed_section_head(entries, len(wire), addends.nbytes if bias else None)
     raws = [v.tobytes() for e, v in zip(entries, records.values()) if e.coding == RAW]
-    section = head + (addends.tobytes() if bias else b"") + wire + b"".join(raws)
+    section = plan.head(len(wire)) + addends.tobytes() + wire + b"".join(raws)
     del keep
-    version = PACKED_BIAS_VERSION if bias else PACKED_VERSION
-    return (struct.pack("<7Q", TRACE_MAGIC, version, jl, po, ps, ro, len(section)) + bytes(buf[56:ro]) + section)
+    return (struct.pack("<7Q", TRACE_MAGIC, plan.version, jl, po, ps, ro, len(section)) + bytes(buf[56:ro]) + section)
 
 
 @dataclass
@@ -574,7 +616,8 @@ class PackedFile:
     size: int
     version: int = PACKED_VERSION
     addend_off: int = 0    # version 3: the addends part (it ends where the wire starts)
-    addend_size: int = 0
+    addend_size: int = 0   # as the file states it
+    plan: Optional[PackedPlan] = None   # of ``entries`` and ``version``
 
 
 def parse_packed(buf) -> PackedFile:
@@ -591,7 +634,7 @@ def parse_packed(buf) -> PackedFile:
     try:
         json_text = bytes(buf[56:56 + jl]).decode()
         magic, n, plan_len, wire_size, raw_size, *rest = section.unpack_from(buf, ro)
-        addend_size = rest[0] if v3 else 0
+        addend_size = rest[0] if rest else 0
         if magic != PACK_MAGIC:
             raise ValueError("packed trace: bad records section")
         addend_off = ro + _align(section.size + plan_len, 8)
@@ -617,11 +660,11 @@ def parse_packed(buf) -> PackedFile:
             if e.addend_off % 4 or e.addend_off + 4 * e.channels > addend_size:
                 raise ValueError(f"record {e.name}: its addends do not lie inside the addends part")
         elif (WIRE_KIND.get(e.dtype) != e.coding or not 1 <= _n_elems(e.shape) <= 1 << 40 or e.diff not in (0, 1) or
-              (e.diff and (before is None or (_seg_kind(before.coding) if v3 else before.coding) != e.coding or
+              (e.diff and (before is None or _seg_kind(before.coding) != e.coding or
                            _n_elems(before.shape) != _n_elems(e.shape)))):
             raise ValueError(f"record {e.name}: coding {e.coding} / diff {e.diff} does not fit the record list")
     return PackedFile(json_text, po, ps, entries, wire_off, wire_size, wire_off + wire_size, raw_size, size,
-                      int(version), addend_off, addend_size)
+                      int(version), addend_off, addend_size, PackedPlan(entries, int(version)))
 
 
 def unpack_trace(path_or_bytes) -> bytearray:
@@ -633,7 +676,6 @@ def unpack_trace(path_or_bytes) -> bytearray:
     outside it."""
     buf = _open(path_or_bytes)
     pf = parse_packed(buf)
-    lib = _lib.load()
     params = parse_ndarray_list(buf, pf.params_off, pf.params_size)
     p_items = [(k, v.shape, str(v.dtype)) for k, v in params.items()]
     r_items = [(e.name, e.shape, e.dtype) for e in pf.entries]
@@ -652,20 +694,14 @@ def unpack_trace(path_or_bytes) -> bytearray:
         if po != pf.params_off or po + pf.params_size > len(image):
             raise ValueError("packed trace: the params blob does not lie where the header says")
         image[po:po + pf.params_size] = buf[pf.params_off:pf.params_off + pf.params_size]
-        recs, n = _wire_records(pf.entries, layout.record_offsets)
+        recs, n = pf.plan.wire_records(layout.record_offsets)
         if n:
             base, keep = _ptr(buf)
-            if pf.version == PACKED_BIAS_VERSION:
-                # (the addends part is 8-byte aligned in the file; mapped or copied, in memory too)
-                rc = lib.tk_wire_decode_bias(recs, _wire_addends(pf.entries, base + pf.addend_off), n,
-                                             ctypes.c_void_p(base + pf.wire_off), pf.wire_size,
-                                             ctypes.c_void_p(ctypes.addressof(cbuf)), len(image), 0)
-            else:
-                rc = lib.tk_wire_decode(recs, n, ctypes.c_void_p(base + pf.wire_off), pf.wire_size,
-                                        ctypes.c_void_p(ctypes.addressof(cbuf)), len(image), 0)
+            # (the addends part is 8-byte aligned in the file; mapped or copied, in memory too)
+            wire_call("tk_wire_decode", recs, pf.plan.wire_addends(base + pf.addend_off), n,
+                      ctypes.c_void_p(base + pf.wire_off), pf.wire_size, ctypes.c_void_p(ctypes.addressof(cbuf)),
+                      len(image), 0, reader=True)
             del keep
-            if rc != 0:
-                raise ValueError("packed trace: " + lib.tk_last_error().decode(errors="replace"))
         elif pf.wire_size:
             raise ValueError("packed trace: a wire buffer without coded records")
         for e, off in zip(pf.entries, layout.record_offsets):
@@ -726,18 +762,12 @@ def check_trace(buf, records, params=None) -> CheckedTrace:
         except ValueError:
             raise ValueError("packed trace: the header json does not parse") from None
         entries, po, ps = pf.entries, pf.params_off, pf.params_size
-        recs, n = _wire_records(entries, [0] * len(entries))
+        recs, n = pf.plan.wire_records()
         if n:
             base, keep = _ptr(buf)
-            lib = _lib.load()
-            if version == PACKED_BIAS_VERSION:
-                rc = lib.tk_wire_check_bias(recs, _wire_addends(entries, base + pf.addend_off), n,
-                                            ctypes.c_void_p(base + pf.wire_off), pf.wire_size)
-            else:
-                rc = lib.tk_wire_check(recs, n, ctypes.c_void_p(base + pf.wire_off), pf.wire_size)
+            wire_call("tk_wire_check", recs, pf.plan.wire_addends(base + pf.addend_off), n,
+                      ctypes.c_void_p(base + pf.wire_off), pf.wire_size, reader=True)
             del keep
-            if rc != 0:
-                raise ValueError("packed trace: " + lib.tk_last_error().decode(errors="replace"))
         elif pf.wire_size:
             raise ValueError("packed trace: a wire buffer without coded records")
         addend_size = pf.addend_size
@@ -789,7 +819,7 @@ def packed_info(path_or_bytes) -> Dict[str, Any]:
             "plan": [dict({"name": e.name, "dtype": e.dtype, "shape": list(e.shape),
                            "coding": "raw" if e.coding == RAW else e.coding, "diff": e.diff},
                           **({"axis": e.axis} if e.coding == BIAS else {})) for e in pf.entries]}
-    if pf.version == PACKED_BIAS_VERSION:
+    if pf.plan.bias:
         info["addend_bytes"] = pf.addend_size
     return info
 

@@ -197,14 +197,15 @@ static void check_plan(const Net& net, const tk::CaptureOptions& opt, const tk::
         CHECK(d.prev == (pv ? (const char*)pv->src + esize * e0 : nullptr));
         CHECK(h.prev == (pv ? pv->host + esize * e0 : nullptr));
         if (r.bias) {
-          CHECK(d.addend == kAddendDev + r.addend_at && h.addend == kAddendHost + r.addend_at);
-          CHECK(d.plane == r.plane && d.channels == r.channels && h.plane == r.plane && h.channels == r.channels);
+          const tk::WireBias &db = d.bias, &hb = h.bias;
+          CHECK(db.addend == kAddendDev + r.addend_at && hb.addend == kAddendHost + r.addend_at);
+          CHECK(db.plane == r.plane && db.channels == r.channels && hb.plane == r.plane && hb.channels == r.channels);
           const int32_t c0 = (int32_t)((e0 / r.plane) % r.channels), r0 = (int32_t)(e0 % r.plane);
-          CHECK(d.c0 == c0 && d.r0 == r0 && h.c0 == c0 && h.r0 == r0);
+          CHECK(db.c0 == c0 && db.r0 == r0 && hb.c0 == c0 && hb.r0 == r0);
           const tk::WireSegPos pos = tk::wire_seg_pos(e0, r.plane, r.channels);
           CHECK(pos.c0 == c0 && pos.r0 == r0);
         } else {
-          CHECK(!d.addend && !h.addend && !d.plane && !d.channels && !h.plane && !h.channels);
+          CHECK(!d.bias.addend && !h.bias.addend && !d.bias.plane && !d.bias.channels && !h.bias.plane && !h.bias.channels);
         }
         chain_of_seg.push_back(chain);
       }
@@ -305,7 +306,7 @@ static void check_model() {
       const tk::CaptureRecord* conv = rec_of(p, 0, 0);
       CHECK(w.segs.size() == 2 && w.units.size() == 2 && w.units[0].count == 1 && w.units[1].count == 1);
       CHECK(w.segs[0].prev == conv->host && w.segs[1].prev == conv->host + 4 * tk::kWireSegElems);
-      CHECK(p.wire_segs[w.seg_off].prev == conv->src && w.segs[1].c0 == (tk::kWireSegElems / 289) % 24);
+      CHECK(p.wire_segs[w.seg_off].prev == conv->src && w.segs[1].bias.c0 == (tk::kWireSegElems / 289) % 24);
       CHECK(p.wchunks[3].units.size() == 2 && p.wchunks[3].units[0].count == 1 && p.wchunks[3].segs[0].prev == rec_of(p, 2, 0)->host);
       // in one chunk the same records are chained
       tk::CapturePlan one;
