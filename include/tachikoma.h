@@ -939,6 +939,70 @@ int tk_stats_plan_run(tk_stats_plan* plan, tk_record_stats* stats_dev, void* str
 int tk_record_stats_batch(const void* const* src, const int64_t* n_elems, const int32_t* kinds, int n,
                           tk_record_stats* out_host, void* stream);
 
+/* Float statistics: what relay.quantize's dataset calibration reduces float32 records to.
+ *
+ * The float32 twin of the block above, for the records of a float profile graph (tk_record_stats
+ * leaves float32 out): three passes over the n records of a plan, each exactly one launch on
+ * `stream` that uploads nothing and synchronises nothing, each merging into device-resident
+ * results, so a dataset is calibrated run after run and only the results cross the link.  Every
+ * result is determined by integers (counts, and min / max merged through an order-preserving
+ * integer view of the float), so it does not depend on arrival order and is equal on every run.
+ * A workgroup takes tk_fstats_span() consecutive elements of one record (a record of more than 512
+ * spans is cut into 512 runs of a whole number of spans), a lane 16 bytes at a time where the
+ * buffer is 16-byte aligned, element by element at a ragged end and in a buffer that is only
+ * 4-byte aligned; every byte is read once per pass and a workgroup flushes once, with integer
+ * atomics on its non-zero bins only.
+ *
+ * tk_fstats_plan_range: per record `count` elements, `nonfinite` of them NaN or +-inf, and `min` /
+ * `max` of the finite ones (+inf / -inf while there is none; -0.0 and denormals are ordinary values,
+ * -0.0 ordered below +0.0).  tk_float_range_reset writes that identity into n entries (device
+ * memory, 8-byte aligned).
+ *
+ * tk_fstats_plan_histogram: np.histogram's counts over given edges.  edges_dev holds bins + 1
+ * float32 edges per record (n x (bins + 1), non-decreasing), hist_dev bins 64-bit counts per record
+ * (n x bins); the caller zeroes hist_dev and calls accumulate.  An element x is counted in bin i
+ * when edges[i] <= x < edges[i + 1]; the last bin also takes x == edges[bins]; an element outside
+ * [edges[0], edges[bins]] or a NaN is counted nowhere.  The bin is estimated in float32 and then
+ * stepped down and up against the edges, so the edges alone define the result, as they do in
+ * numpy (numpy/lib/_histograms_impl.py, the equal-bins path).  2 <= bins <= 8192.
+ *
+ * tk_fstats_plan_digits: one level of an exact radix select of |x|.  The 31 magnitude bits of a
+ * float32 order as an unsigned integer and are split 11 + 10 + 10: level 0 counts every element in
+ * the bin of bits 30..20 (non-finite values fall into digits >= 0x7F8), level 1 the elements whose
+ * bits 30..20 equal prefix_dev[record] in the bin of bits 19..10, level 2 those whose bits 30..10
+ * equal it in the bin of bits 9..0.  hist_dev holds 2048 64-bit counts per record (n x 2048; levels
+ * 1 and 2 use the first 1024), zeroed by the caller; calls accumulate.  The sign bit is cleared
+ * first, so -0.0 counts as 0.
+ *
+ * tk_fstats_plan_create lays out and uploads the job table of n records (src[i]: device buffer of
+ * n_elems[i] float32); the plan owns it.  A record of no elements is allowed and its entries are
+ * never touched.  The *_batch forms are one-shot -- plan, identity, one pass, copy into the host
+ * result, synchronise `stream`, destroy -- and take their edges / prefixes from host memory.
+ * Refused before any launch with TK_ERR_INVALID_ARG: a null argument, n <= 0, a negative count, a
+ * buffer that is not 4-byte aligned, bins outside 2..8192, a level outside 0..2 or more workgroups
+ * than one launch takes. */
+typedef struct {
+  uint64_t count;
+  uint64_t nonfinite;
+  float min, max;
+} tk_float_range;
+typedef struct tk_fstats_plan tk_fstats_plan;
+int tk_fstats_span(void);
+int tk_float_range_size(void); /* sizeof(tk_float_range), for the binding */
+int tk_fstats_plan_create(const void* const* src, const int64_t* n_elems, int n, tk_fstats_plan** out);
+int tk_fstats_plan_destroy(tk_fstats_plan* plan);
+int tk_float_range_reset(tk_float_range* ranges_dev, int n, void* stream);
+int tk_fstats_plan_range(tk_fstats_plan* plan, tk_float_range* ranges_dev, void* stream);
+int tk_fstats_plan_histogram(tk_fstats_plan* plan, const float* edges_dev, int bins, uint64_t* hist_dev, void* stream);
+int tk_fstats_plan_digits(tk_fstats_plan* plan, int level, const uint32_t* prefix_dev, uint64_t* hist_dev,
+                          void* stream);
+int tk_float_range_batch(const void* const* src, const int64_t* n_elems, int n, tk_float_range* out_host,
+                         void* stream);
+int tk_float_histogram_batch(const void* const* src, const int64_t* n_elems, int n, const float* edges_host, int bins,
+                             uint64_t* hist_host, void* stream);
+int tk_float_digits_batch(const void* const* src, const int64_t* n_elems, int n, int level, const uint32_t* prefix_host,
+                          uint64_t* hist_host, void* stream);
+
 /* Makes `stream` wait for the copies of the last traced run: call before writing any
  * tensor the module reads (GraphModule.set_input / load_params,
  * graph_executor.cc:158-166 SetInput) on a stream of your own. */

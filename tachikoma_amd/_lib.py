@@ -349,6 +349,15 @@ class tk_record_stats(ctypes.Structure):
     ]
 
 
+class tk_float_range(ctypes.Structure):
+    _fields_ = [
+        ("count", ctypes.c_uint64),
+        ("nonfinite", ctypes.c_uint64),  # NaN and +-inf
+        ("min", ctypes.c_float),         # of the finite values; +inf while there is none
+        ("max", ctypes.c_float),         # -inf while there is none
+    ]
+
+
 TK_WIRE_UNPACK_STORE, TK_WIRE_UNPACK_COMPARE = 0, 1
 NO_MISMATCH = 0xFFFFFFFFFFFFFFFF
 
@@ -502,6 +511,20 @@ SIGNATURES = {
     "tk_stats_plan_run": (ctypes.c_int, [_VP, _VP, _VP]),
     "tk_record_stats_batch": (ctypes.c_int, [ctypes.POINTER(_VP), ctypes.POINTER(_I64), ctypes.POINTER(ctypes.c_int32),
                                              ctypes.c_int, _VP, _VP]),
+    "tk_fstats_span": (ctypes.c_int, []),
+    "tk_float_range_size": (ctypes.c_int, []),
+    "tk_fstats_plan_create": (ctypes.c_int, [ctypes.POINTER(_VP), ctypes.POINTER(_I64), ctypes.c_int,
+                                             ctypes.POINTER(_VP)]),
+    "tk_fstats_plan_destroy": (ctypes.c_int, [_VP]),
+    "tk_float_range_reset": (ctypes.c_int, [_VP, ctypes.c_int, _VP]),
+    "tk_fstats_plan_range": (ctypes.c_int, [_VP, _VP, _VP]),
+    "tk_fstats_plan_histogram": (ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, _VP]),
+    "tk_fstats_plan_digits": (ctypes.c_int, [_VP, ctypes.c_int, _VP, _VP, _VP]),
+    "tk_float_range_batch": (ctypes.c_int, [ctypes.POINTER(_VP), ctypes.POINTER(_I64), ctypes.c_int, _VP, _VP]),
+    "tk_float_histogram_batch": (ctypes.c_int, [ctypes.POINTER(_VP), ctypes.POINTER(_I64), ctypes.c_int, _VP,
+                                                ctypes.c_int, _VP, _VP]),
+    "tk_float_digits_batch": (ctypes.c_int, [ctypes.POINTER(_VP), ctypes.POINTER(_I64), ctypes.c_int, ctypes.c_int,
+                                             _VP, _VP, _VP]),
     "tk_module_tune": (ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32),
                                       ctypes.POINTER(_F32)]),
     "tk_module_set_node_algo": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int]),

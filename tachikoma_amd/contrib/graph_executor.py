@@ -19,8 +19,8 @@ import numpy as np
 from .. import _lib
 from .. import trace_format as tf
 from ..relay.device_module import DeviceModule
-from .trace_device import (FaultyNode, FaultyOp, Mismatch, PackedCapture, ReplayReport, StatsAccumulator,  # noqa: F401
-                           TraceCapture, TraceVerifier, VerifyReport)
+from .trace_device import (FaultyNode, FaultyOp, FloatStatsAccumulator, Mismatch, PackedCapture,  # noqa: F401
+                           ReplayReport, StatsAccumulator, TraceCapture, TraceVerifier, VerifyReport)
 
 
 class NDArrayView:
@@ -511,6 +511,14 @@ class GraphModule:
         each run, ``result()`` at the end (StatsAccumulator).  Its device memory lives until it or
         this module is closed."""
         acc = StatsAccumulator(self.module, self.module.stats_plan(names))
+        self._accumulators.append(acc)
+        return acc
+
+    def float_stats_accumulator(self, names=None) -> FloatStatsAccumulator:
+        """A fresh float statistics accumulator over the float32 records ``names`` (default: all
+        of them): ranges, edge histograms and radix-select digit counts kept on the device
+        (FloatStatsAccumulator).  Its device memory lives until it or this module is closed."""
+        acc = FloatStatsAccumulator(self.module, self.module.float_stats_plan(names))
         self._accumulators.append(acc)
         return acc
 

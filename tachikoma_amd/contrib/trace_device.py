@@ -1,6 +1,7 @@
 """The device side of trace files, which GraphModule (graph_executor.py) drives: the captures that write
 them (TraceCapture, PackedCapture), the verifier that checks, loads and replays them (TraceVerifier and
-its reports) and the per-record statistics (StatsAccumulator)."""
+its reports), the per-record statistics (StatsAccumulator) and the float statistics of a profile graph
+(FloatStatsAccumulator)."""
 from __future__ import annotations
 
 import ctypes
@@ -573,3 +574,178 @@ class StatsAccumulator:
 
     def close(self) -> None:
         self._dev = None
+
+
+@dataclass
+class FloatRange:
+    """One tk_float_range entry: ``count`` elements, ``nonfinite`` of them NaN or +-inf, ``min`` /
+    ``max`` of the finite ones as np.float32 (+inf / -inf while there is none)."""
+    count: int
+    nonfinite: int
+    min: np.float32
+    max: np.float32
+
+
+RANGE_DTYPE = np.dtype([("count", "<u8"), ("nonfinite", "<u8"), ("min", "<f4"), ("max", "<f4")])
+DIGIT_BINS = 2048  # entries of a record's digit table (levels 1 and 2 use the first 1024)
+
+
+class FloatStatsAccumulator:
+    """Float statistics accumulated on the device (tk_fstats_plan_* into device-resident results),
+    for the float32 records of a profile graph: after each run ``add_range``, ``add_histogram`` or
+    ``add_digits`` merges the record buffers as they stand -- one launch, nothing uploaded, nothing
+    waited for -- and only ``ranges``, ``histograms`` and ``digits`` copy results out and
+    synchronise.  The histogram follows np.histogram over the edges ``set_edges`` builds from the
+    accumulated ranges; the digit counts serve an exact radix select of |x|
+    (relay.quantize.passes.radix_select).  The device memory is released by ``close`` or when the
+    module is closed."""
+
+    def __init__(self, module: DeviceModule, plan):
+        import torch
+        self.module, self.plan = module, plan
+        self.names = list(plan.names)
+        self._n = max(1, len(self.names))
+        self._ranges = torch.empty(self._n * RANGE_DTYPE.itemsize // 8, dtype=torch.int64, device=module.device)
+        self._edges = self._hist = self._digits = self._prefix = None
+        self._edges_host: Optional[np.ndarray] = None
+        self._known: Optional[Dict[str, FloatRange]] = None  # the ranges as last read, None once they grew
+        self._keep: List[Any] = []                           # pinned sources of uploads in flight
+        self.bins = 0
+        self._digit_key = None
+        self.reset_ranges()
+
+    def _stream(self, stream=None):
+        import torch
+        return torch.cuda.current_stream(self.module.device) if stream is None else stream
+
+    def _handle(self, stream) -> ctypes.c_void_p:
+        return ctypes.c_void_p(_lib.stream_handle(self._stream(stream)))
+
+    def _live(self) -> None:
+        if self._ranges is None or self.module.closed:
+            raise _lib.TachikomaError("the float statistics accumulator was closed (with its module)")
+
+    def _upload(self, array: np.ndarray, dev, stream) -> None:
+        import torch
+        host = torch.from_numpy(np.ascontiguousarray(array).view(np.int32).reshape(-1)).pin_memory()
+        self._keep = self._keep[-3:] + [host]
+        with torch.cuda.stream(self._stream(stream)):
+            dev.copy_(host, non_blocking=True)
+
+    def _download(self, dev, stream) -> np.ndarray:
+        import torch
+        s = self._stream(stream)
+        with torch.cuda.stream(s):
+            host = dev.to("cpu", non_blocking=True)
+        s.synchronize()
+        return host.numpy()
+
+    def reset_ranges(self, stream=None) -> None:
+        """The ranges back to the identity (no elements), enqueued on the stream."""
+        self._live()
+        self._known = None
+        if self.names:
+            _lib.check(self.module.lib.tk_float_range_reset(ctypes.c_void_p(self._ranges.data_ptr()), len(self.names),
+                                                            self._handle(stream)), "tk_float_range_reset")
+
+    def add_range(self, stream=None) -> None:
+        """Merge the records' ranges as the buffers stand: one launch on ``stream`` (default: the
+        current one, where the run was enqueued)."""
+        self._live()
+        self._known = None
+        if self.names:
+            _lib.check(self.module.lib.tk_fstats_plan_range(self.plan.handle, ctypes.c_void_p(self._ranges.data_ptr()),
+                                                            self._handle(stream)), "tk_fstats_plan_range")
+
+    def ranges(self, stream=None) -> Dict[str, FloatRange]:
+        """{name: FloatRange} of everything added since the last reset: one copy, one synchronisation."""
+        self._live()
+        rows = self._download(self._ranges, stream).view(RANGE_DTYPE)
+        self._known = {n: FloatRange(int(r["count"]), int(r["nonfinite"]), np.float32(r["min"]), np.float32(r["max"]))
+                       for n, r in zip(self.names, rows)}
+        return dict(self._known)
+
+    def set_edges(self, bins: int, stream=None) -> None:
+        """Give every record numpy's own ``bins + 1`` float32 edges over (-thres, thres), thres the
+        larger magnitude of its accumulated range (relay.quantize.passes.histogram_edges), upload
+        them and zero the histograms.  Reads the ranges (``ranges()``) unless they were read since
+        the last ``add_range``; a record without finite values is a ValueError."""
+        import torch
+        from ..relay.quantize.passes import histogram_edges
+        self._live()
+        if not 2 <= bins <= 8192:
+            raise ValueError(f"set_edges: bins must lie in 2..8192, not {bins}")
+        known = self._known if self._known is not None else self.ranges(stream)
+        edges = np.zeros((self._n, bins + 1), np.float32)
+        for i, name in enumerate(self.names):
+            r = known[name]
+            if r.nonfinite or not (np.isfinite(r.min) and np.isfinite(r.max)):
+                raise ValueError(f"set_edges: record {name} has no finite range "
+                                 f"({r.count} values, {r.nonfinite} of them NaN or infinite)")
+            edges[i] = histogram_edges(r.min, r.max, bins)
+        dev = self.module.device
+        self.bins, self._edges_host = bins, edges
+        self._edges = torch.empty(self._n * (bins + 1), dtype=torch.int32, device=dev)
+        self._upload(edges, self._edges, stream)
+        with torch.cuda.stream(self._stream(stream)):
+            self._hist = torch.zeros(self._n * bins, dtype=torch.int64, device=dev)
+
+    def add_histogram(self, stream=None) -> None:
+        """Count the record buffers as they stand into the histograms: one launch on ``stream``."""
+        self._live()
+        if self._hist is None:
+            raise ValueError("add_histogram: set_edges first")
+        if self.names:
+            _lib.check(self.module.lib.tk_fstats_plan_histogram(
+                self.plan.handle, ctypes.c_void_p(self._edges.data_ptr()), self.bins,
+                ctypes.c_void_p(self._hist.data_ptr()), self._handle(stream)), "tk_fstats_plan_histogram")
+
+    def histograms(self, stream=None) -> Dict[str, Tuple[np.ndarray, np.ndarray]]:
+        """{name: (counts, edges)} as np.histogram returns them (uint64 counts, float32 edges) of
+        everything added since ``set_edges``: one copy, one synchronisation."""
+        self._live()
+        if self._hist is None:
+            raise ValueError("histograms: set_edges first")
+        counts = self._download(self._hist, stream).view(np.uint64).reshape(self._n, self.bins)
+        return {n: (counts[i].copy(), self._edges_host[i].copy()) for i, n in enumerate(self.names)}
+
+    def add_digits(self, level: int, prefixes=None, stream=None) -> None:
+        """Count one level of the radix select of |x| over the record buffers as they stand: one
+        launch on ``stream``.  ``prefixes`` holds, per record in ``names`` order, the bits of |x|
+        above the level's digit (None at level 0).  Calls with the same level and prefixes
+        accumulate; another level or other prefixes zero the tables and upload the prefixes first."""
+        import torch
+        self._live()
+        if level not in (0, 1, 2):
+            raise ValueError(f"add_digits: level must be 0, 1 or 2, not {level}")
+        pre = [0] * len(self.names) if prefixes is None else [int(p) for p in prefixes]
+        if len(pre) != len(self.names):
+            raise ValueError(f"add_digits: {len(pre)} prefixes for {len(self.names)} records")
+        key = (level, tuple(pre))
+        if key != self._digit_key:
+            dev = self.module.device
+            if self._prefix is None:
+                self._prefix = torch.empty(self._n, dtype=torch.int32, device=dev)
+                self._digits = torch.empty(self._n * DIGIT_BINS, dtype=torch.int64, device=dev)
+            self._upload(np.array(pre + [0] * (self._n - len(pre)), np.uint32), self._prefix, stream)
+            with torch.cuda.stream(self._stream(stream)):
+                self._digits.zero_()
+            self._digit_key = key
+        if self.names:
+            _lib.check(self.module.lib.tk_fstats_plan_digits(
+                self.plan.handle, level, ctypes.c_void_p(self._prefix.data_ptr()),
+                ctypes.c_void_p(self._digits.data_ptr()), self._handle(stream)), "tk_fstats_plan_digits")
+
+    def digits(self, stream=None) -> Dict[str, np.ndarray]:
+        """{name: uint64 counts per digit} of the level last added (2048 entries at level 0, 1024
+        below): one copy, one synchronisation."""
+        self._live()
+        if self._digits is None:
+            raise ValueError("digits: add_digits first")
+        used = DIGIT_BINS if self._digit_key[0] == 0 else DIGIT_BINS // 2
+        counts = self._download(self._digits, stream).view(np.uint64).reshape(self._n, DIGIT_BINS)
+        return {n: counts[i, :used].copy() for i, n in enumerate(self.names)}
+
+    def close(self) -> None:
+        self._ranges = self._edges = self._hist = self._digits = self._prefix = None
+        self._keep = []

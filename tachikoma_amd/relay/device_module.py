@@ -1176,9 +1176,45 @@ class DeviceModule:
             if p.handle:
                 self.lib.tk_stats_plan_destroy(p.handle)
                 p.handle = ctypes.c_void_p()
+        for p in self.__dict__.pop("_fstats_plans", {}).values():
+            if p.handle:
+                self.lib.tk_fstats_plan_destroy(p.handle)
+                p.handle = ctypes.c_void_p()
+
+    def float_stats_plan(self, names=None) -> "FloatStatsPlan":
+        """The float statistics plan (tk_fstats_plan) over the float32 record buffers ``names``
+        (default: every float32 record of plan.records, in trace order), built once per name tuple
+        and kept until close().  A name that is no record is a KeyError, a record that is not
+        float32 a ValueError."""
+        recs = {t.name: t for t in self.plan.records}
+        key = (tuple(n for n, t in recs.items() if str(t.dtype) == "float32") if names is None else tuple(names))
+        plans = self.__dict__.setdefault("_fstats_plans", {})
+        if key not in plans:
+            for name in key:
+                if name not in recs:
+                    raise KeyError(f"float_stats_plan: {name} is not a record of the graph")
+                if str(recs[name].dtype) != "float32":
+                    raise ValueError(f"float_stats_plan: record {name} is {recs[name].dtype}, not float32")
+            handle = ctypes.c_void_p()
+            if key:
+                n = len(key)
+                src = (ctypes.c_void_p * n)(*[self.buffers[k].data_ptr() for k in key])
+                counts = (ctypes.c_int64 * n)(*[self.buffers[k].numel() for k in key])
+                _lib.check(self.lib.tk_fstats_plan_create(src, counts, n, ctypes.byref(handle)),
+                           "tk_fstats_plan_create")
+            plans[key] = FloatStatsPlan(handle, key)
+        return plans[key]
 
     def output(self, name: str):
         return self.buffers[name]
+
+
+class FloatStatsPlan:
+    """A native float statistics plan and the ``names`` of the float32 records it reduces, in the
+    order of the result arrays' entries."""
+
+    def __init__(self, handle, names):
+        self.handle, self.names = handle, list(names)
 
 
 class StatsPlan:

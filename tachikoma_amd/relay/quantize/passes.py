@@ -469,14 +469,24 @@ def find_scale_by_kl(arr: np.ndarray, quantized_dtype: str = "int8", num_bins: i
     instead (a meaningful threshold for float64 statistics, where the reference's is not)."""
     if edges_as not in ("reference", "values"):
         raise ValueError(f"find_scale_by_kl: edges_as must be 'reference' or 'values', not {edges_as!r}")
-    import ctypes
-    from ... import _lib
     arr = np.asarray(arr)
     min_val, max_val = np.min(arr), np.max(arr)
     thres = max(abs(min_val), abs(max_val))
+    hist, edges = np.histogram(arr, bins=num_bins, range=(-thres, thres))
+    return kl_threshold(hist, edges, min_val, quantized_dtype, num_bins, num_quantized_bins, edges_as)
+
+
+def kl_threshold(hist: np.ndarray, edges: np.ndarray, min_val, quantized_dtype: str = "int8", num_bins: int = 8001,
+                 num_quantized_bins: int = 255, edges_as: str = "reference") -> float:
+    """The part of ``find_scale_by_kl`` after the histogram: ``hist`` (num_bins counts) and
+    ``edges`` (np.histogram's edge array) go to the native MinimizeKL, with the doubled quantized
+    bins of a non-negative record under uint8.  The device calibration (``device_scales``) calls it
+    with the device's counts.  The counts are cast to int32 as they are: ``find_scale_by_kl``
+    wraps a count above INT32_MAX there, ``device_scales`` raises a ValueError before it calls."""
+    import ctypes
+    from ... import _lib
     if min_val >= 0 and quantized_dtype in ["uint8"]:
         num_quantized_bins = num_quantized_bins * 2 + 1
-    hist, edges = np.histogram(arr, bins=num_bins, range=(-thres, thres))
     hist = np.ascontiguousarray(hist, np.int32)
     edges = kl_edge_buffer(edges, num_bins) if edges_as == "reference" else np.ascontiguousarray(edges, np.float32)
     out = ctypes.c_float()
@@ -496,21 +506,142 @@ def kl_edge_buffer(edges: np.ndarray, num_bins: int) -> np.ndarray:
     return np.frombuffer(raw.tobytes()[:4 * (num_bins + 1)], np.float32).copy()
 
 
-def _dataset_scales(mod, dataset, finder) -> List[float]:
+def histogram_edges(min_val, max_val, bins: int = 8001) -> np.ndarray:
+    """The float32 edges np.histogram gives ``find_scale_by_kl`` for float32 values of the range
+    [min_val, max_val]: numpy's own, over ``range=(-thres, thres)`` with the float32
+    ``thres = max(|min|, |max|)`` (an all-zero record gets numpy's widening to (-0.5, 0.5))."""
+    thres = max(abs(np.float32(min_val)), abs(np.float32(max_val)))
+    return np.histogram(np.zeros(0, np.float32), bins=bins, range=(-thres, thres))[1]
+
+
+SELECT_DIGITS = ((0, 11), (1, 10), (2, 10))  # (level, bits of its digit): bits 30..20, 19..10, 9..0 of |x|
+
+
+def radix_select(count, ks) -> List[int]:
+    """The exact k-th smallest |x| (k zero-based, as in ``np.partition(np.abs(x), k)[k]``) of several
+    float32 records at once, as uint32 bit patterns, from three rounds of digit counts.
+
+    The 31 magnitude bits of a float32 order as an unsigned integer.  ``count(level, prefixes)``
+    returns, per record, the number of elements in each digit of ``level`` among those whose bits
+    above that digit equal the record's prefix (level 0: 2048 digits, no prefix; levels 1 and 2:
+    1024 digits).  Each round picks the digit that holds rank k and takes the counts below it off
+    k.  The counting step is the caller's: tk_fstats_plan_digits on the device, numpy in tests.
+    ``ks`` holds one rank per record, or is a function of a record's element count (the total of
+    its level-0 counts) where the rank depends on it; ``prefixes`` of the first round is None."""
+    prefixes: Optional[List[int]] = None
+    rest: List[int] = []
+    for level, width in SELECT_DIGITS:
+        tables = count(level, None if prefixes is None else list(prefixes))
+        if prefixes is None:
+            prefixes = [0] * len(tables)
+            rest = [int(ks(int(np.asarray(t, np.uint64).sum()))) for t in tables] if callable(ks) else [int(k) for k in ks]
+        for i, table in enumerate(tables):
+            cum = np.cumsum(np.asarray(table, np.uint64)[:1 << width], dtype=np.uint64)
+            if rest[i] < 0 or rest[i] >= int(cum[-1]):
+                raise ValueError(f"radix_select: the rank lies outside record {i}")
+            digit = int(np.searchsorted(cum, np.uint64(rest[i]), side="right"))
+            rest[i] -= int(cum[digit - 1]) if digit else 0
+            prefixes[i] = (prefixes[i] << width) | digit
+    return prefixes
+
+
+def device_scales(mod, dataset, mode: str, percentile: float = 0.99999, num_bins: int = 8001) -> List[float]:
+    """The per-layer scales of ``collect_stats`` + ``find_scale_by_kl`` / ``find_scale_by_percentile``,
+    equal to theirs, with the reductions done where the activations lie (tk_fstats.hip): the
+    profile graph is built once, as ``collect_stats`` builds it, and run over the dataset
+
+    - ``kl_divergence``: twice -- ranges, then the ``num_bins`` histogram over numpy's own edges of
+      that range (``histogram_edges``), whose counts go to ``kl_threshold``;
+    - ``percentile``: three times -- the digit counts of ``radix_select`` for
+      k = int(count * percentile); the scale is the selected bit pattern.
+
+    No activation leaves the device: per layer only the range, one histogram or three digit tables
+    do.  The graph runs passes x len(dataset) times whatever ``calibrate_chunk_by`` says: that
+    setting bounds the host memory of ``collect_stats`` and is ignored here.
+
+    Deviations from the host path: a record with NaN or +-inf values raises a ValueError that names
+    it in both modes (``find_scale_by_kl`` raises there too, from np.histogram's range check;
+    ``find_scale_by_percentile`` does not), and a histogram count above INT32_MAX raises a
+    ValueError where the host path's int32 cast wraps."""
+    if mode not in ("kl_divergence", "percentile"):
+        raise ValueError(f"device_scales: mode must be kl_divergence or percentile, not {mode!r}")
+    from ..build_module import build
+    from ...contrib.graph_executor import GraphModule
+    dataset = list(dataset)
+    prof, targets = stats_profile(mod)
+    names: Dict[int, str] = {}
+    counter = 0
+    for n in post_order(prof["main"].body):
+        if isinstance(n, Var):
+            names[id(n)] = n.name_hint
+        elif isinstance(n, Call):
+            names[id(n)] = f"%{counter}"
+            counter += 1
+    tnames = [names[id(t)] for t in targets]
+    uniq = list(dict.fromkeys(tnames))
+    gm = GraphModule(build(prof, target="mi355x")["default"]())
+    try:
+        acc = gm.float_stats_accumulator(uniq)
+
+        def sweep(step) -> None:
+            for batch in dataset:
+                gm.set_input(**batch)
+                gm.run()
+                step()
+
+        def refuse_nonfinite(name: str, n: int) -> None:
+            if n:
+                raise ValueError(f"calibrate: record {name} has {n} NaN or infinite values")
+
+        found: Dict[str, float] = {}
+        if mode == "kl_divergence":
+            sweep(acc.add_range)
+            ranges = acc.ranges()
+            for name in uniq:
+                refuse_nonfinite(name, ranges[name].nonfinite)
+            acc.set_edges(num_bins)
+            sweep(acc.add_histogram)
+            for name, (hist, edges) in acc.histograms().items():
+                if hist.size and int(hist.max()) > np.iinfo(np.int32).max:
+                    raise ValueError(f"calibrate: a histogram bin of record {name} holds {int(hist.max())} values, "
+                                     "more than MinimizeKL's int32 counts take")
+                found[name] = kl_threshold(hist, edges, ranges[name].min, "int8", num_bins)
+        else:
+            def count(level, prefixes):
+                sweep(lambda: acc.add_digits(level, prefixes))
+                tables = acc.digits()
+                if level == 0:  # non-finite values have the exponent 0xFF: digits 0x7F8 and above
+                    for name in uniq:
+                        refuse_nonfinite(name, int(tables[name][0x7F8:].sum()))
+                return [tables[name] for name in uniq]
+
+            bits = radix_select(count, lambda total: int(total * percentile))
+            for name, b in zip(uniq, bits):
+                found[name] = float(np.array([b], np.uint32).view(np.float32)[0])
+        return [found[name] for name in tnames]
+    finally:
+        gm.close()
+
+
+def _dataset_scales(mod, dataset, finder, device_stats: bool = False) -> List[float]:
     if dataset is None:
         raise ValueError("calibrate: this calibrate_mode needs a dataset (list of {input name: array})")
     cfg = current_qconfig()
+    if device_stats:
+        return device_scales(mod, dataset, cfg.calibrate_mode)
     scales: List[float] = []
     for samples in collect_stats(mod, list(dataset), cfg.calibrate_chunk_by):
         scales += [finder(s) for s in samples]
     return scales
 
 
-def calibrate(mod, dataset=None) -> IRModule:
+def calibrate(mod, dataset=None, device_stats: bool = False) -> IRModule:
     """_calibrate.py:158-238 (``_set_params``): per simulated_quantize,
     dom_scale = scale / 2^(nbit - sign), clip = +-(2^(nbit - sign) - 1), all float32; the scale
     is ``global_scale``, or found on the dataset (``kl_divergence``, ``percentile``) for inputs and
-    activations, and ``power2`` / ``max`` of the constant for weights."""
+    activations, and ``power2`` / ``max`` of the constant for weights.  With ``device_stats`` the
+    dataset's scales come from ``device_scales`` (equal scales, no activation read back) instead
+    of ``collect_stats`` and the host finders."""
     cfg = current_qconfig()
     wfunc = {"power2": _power2_scale, "max": _max_scale}.get(cfg.weight_scale)
     if wfunc is None:
@@ -519,7 +650,7 @@ def calibrate(mod, dataset=None) -> IRModule:
         dataset_scales = None
     elif cfg.calibrate_mode in ("kl_divergence", "percentile"):
         finder = find_scale_by_kl if cfg.calibrate_mode == "kl_divergence" else find_scale_by_percentile
-        found = _dataset_scales(mod, dataset, finder)
+        found = _dataset_scales(mod, dataset, finder, device_stats)
         n_act = len(stats_profile(mod)[1])
         if len(found) != n_act:
             raise RuntimeError(f"calibrate: {len(found)} profiled scales for {n_act} activation quantizers")
@@ -719,16 +850,16 @@ def realize(mod) -> IRModule:
 
 # ----------------------------------------------------------------------------- driver
 
-def quantize(mod, params=None, dataset=None) -> IRModule:
+def quantize(mod, params=None, dataset=None, device_stats: bool = False) -> IRModule:
     """quantize.py:330-379: prerequisite_optimize -> partition -> annotate -> calibrate ->
-    [realize] -> FoldConstant, under the current ``qconfig``."""
+    [realize] -> FoldConstant, under the current ``qconfig``.  ``device_stats``: see ``calibrate``."""
     cfg = current_qconfig()
     if cfg.partition_conversions not in ("disabled", "enabled", "fully_integral"):
         raise ValueError(f"partition_conversions={cfg.partition_conversions!r}")
     mod = prerequisite_optimize(mod, params)
     mod = partition(mod)
     mod = annotate(mod, _QuantizeContext())
-    mod = calibrate(mod, dataset)
+    mod = calibrate(mod, dataset, device_stats)
     if not cfg.do_simulation:
         mod = realize(mod)
     mod = fold_constant(mod)
