@@ -366,6 +366,57 @@ int tk_dense_f32(const tk_tensor* data, const tk_tensor* weight, tk_tensor* out,
  * (num_quantized_bins buckets) minimises the KL divergence. */
 int tk_find_scale_by_kl(const int32_t* hist, const float* edges, int num_bins, int num_quantized_bins,
                         float* threshold);
+/* Single candidates of that search, evaluated by the very code tk_find_scale_by_kl runs: candidate
+ * k is the window [zero - i, zero + i + 1) with i = num_quantized_bins / 2 + k, zero = num_bins / 2,
+ * 0 <= k <= zero - num_quantized_bins / 2.  Per listed candidate (any order, repeats allowed): the
+ * float32 divergence `div` (+inf where the smoothed q is empty; ps = qs = 0 then), the sequential
+ * float32 sums `ps` / `qs` of the smoothed p and q, and the number of zero entries of p and of q
+ * before smoothing.  Host only.  Refuses an even num_bins: the window only fits an odd count. */
+typedef struct {
+  float div, ps, qs;
+  int32_t p_zeros, q_zeros;
+} tk_kl_candidate;
+int tk_kl_candidate_size(void); /* sizeof(tk_kl_candidate), for the binding */
+int tk_kl_candidates(const int32_t* hist, int num_bins, int num_quantized_bins, const int32_t* cand, int n,
+                     tk_kl_candidate* out);
+
+/* The same search on the device (tk_kl.hip), as intervals: for every candidate of every record the
+ * evaluate kernel writes one tk_kl_row -- `d` the divergence with log and the running sum in
+ * float64 over p, q and p / q that are the host's float32 bits, `bound` a proved bound on
+ * |host div - d| (+inf candidates have d = +inf, bound = 0, as on the host),
+ * ps / qs and the zero counts equal to tk_kl_candidates' -- and the select kernel one tk_kl_pick per
+ * record: the candidates c with d_c - bound_c <= min(d + bound), ascending, their number in `count`
+ * and the first TK_KL_MAX_PICKS of them in `idx`.  The host's argmin (and every earlier tie) is
+ * among them; evaluating them with tk_kl_candidates, first minimum wins, gives the host's choice.
+ * hist_dev: n x num_bins uint64 counts (tk_fstats_plan_histogram's layout); table_dev: n x n_cand
+ * rows, n_cand = num_bins / 2 + 1 - num_quantized_bins / 2; picks_dev: n rows.  Launches two
+ * kernels on `stream`, copies and waits for nothing.  num_bins odd, 3..8191;
+ * 2 <= num_quantized_bins <= num_bins. */
+enum {
+  TK_KL_OK = 0,
+  TK_KL_COUNT_OVERFLOW = 1, /* a count above INT32_MAX: nothing was evaluated */
+  TK_KL_ALL_INF = 2,        /* every candidate is +inf */
+  TK_KL_TOO_MANY = 3,       /* more than TK_KL_MAX_PICKS survivors: idx holds the first ones */
+  TK_KL_MAX_PICKS = 32
+};
+typedef struct {
+  double d, bound;
+  float ps, qs;
+  int32_t p_zeros, q_zeros;
+} tk_kl_row;
+typedef struct {
+  int32_t status, count;
+  int32_t idx[TK_KL_MAX_PICKS];
+} tk_kl_pick;
+int tk_kl_row_size(void);
+int tk_kl_pick_size(void);
+int tk_kl_device(const uint64_t* hist_dev, int n, int num_bins, int num_quantized_bins, tk_kl_row* table_dev,
+                 tk_kl_pick* picks_dev, void* stream);
+/* The kernels of tk_kl_device one at a time, for timing. */
+int tk_kl_device_evaluate(const uint64_t* hist_dev, int n, int num_bins, int num_quantized_bins, tk_kl_row* table_dev,
+                          void* stream);
+int tk_kl_device_select(const uint64_t* hist_dev, int n, int num_bins, int num_quantized_bins,
+                        const tk_kl_row* table_dev, tk_kl_pick* picks_dev, void* stream);
 
 /* ---------------------------------------------------------------- pre-quantized QNN graphs
  * The QNN ops a frontend-produced quantized graph carries besides conv / dense / requantize /

@@ -450,6 +450,14 @@ SIGNATURES = {
     "tk_qnn_binary_fp": (ctypes.c_int, [_PT, _PT, _PT, ctypes.POINTER(tk_qnn_binary_fp_attrs), _VP]),
     "tk_find_scale_by_kl": (ctypes.c_int, [ctypes.POINTER(_I32), ctypes.POINTER(_F32), ctypes.c_int, ctypes.c_int,
                                            ctypes.POINTER(_F32)]),
+    "tk_kl_candidate_size": (ctypes.c_int, []),
+    "tk_kl_candidates": (ctypes.c_int, [ctypes.POINTER(_I32), ctypes.c_int, ctypes.c_int, ctypes.POINTER(_I32), ctypes.c_int,
+                                        _VP]),
+    "tk_kl_row_size": (ctypes.c_int, []),
+    "tk_kl_pick_size": (ctypes.c_int, []),
+    "tk_kl_device": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
+    "tk_kl_device_evaluate": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    "tk_kl_device_select": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
     "tk_module_create": (ctypes.c_int, [ctypes.POINTER(tk_node), ctypes.c_int, ctypes.POINTER(_VP)]),
     "tk_module_destroy": (ctypes.c_int, [_VP]),
     "tk_module_num_nodes": (ctypes.c_int, [_VP]),

@@ -588,6 +588,13 @@ class FloatRange:
 
 RANGE_DTYPE = np.dtype([("count", "<u8"), ("nonfinite", "<u8"), ("min", "<f4"), ("max", "<f4")])
 DIGIT_BINS = 2048  # entries of a record's digit table (levels 1 and 2 use the first 1024)
+# tk_kl_row, tk_kl_pick and tk_kl_candidate (include/tachikoma.h)
+KL_MAX_PICKS = 32
+KL_OK, KL_COUNT_OVERFLOW, KL_ALL_INF, KL_TOO_MANY = 0, 1, 2, 3
+KL_ROW_DTYPE = np.dtype([("d", "<f8"), ("bound", "<f8"), ("ps", "<f4"), ("qs", "<f4"), ("p_zeros", "<i4"),
+                         ("q_zeros", "<i4")])
+KL_PICK_DTYPE = np.dtype([("status", "<i4"), ("count", "<i4"), ("idx", "<i4", (KL_MAX_PICKS,))])
+KL_CANDIDATE_DTYPE = np.dtype([("div", "<f4"), ("ps", "<f4"), ("qs", "<f4"), ("p_zeros", "<i4"), ("q_zeros", "<i4")])
 
 
 class FloatStatsAccumulator:
@@ -612,6 +619,10 @@ class FloatStatsAccumulator:
         self._keep: List[Any] = []                           # pinned sources of uploads in flight
         self.bins = 0
         self._digit_key = None
+        self._kl_table = None                 # device: the last kl_thresholds' rows
+        self._kl_cand = 0
+        self.kl_picks: Optional[np.ndarray] = None  # the last kl_thresholds' pick rows (KL_PICK_DTYPE, one per name)
+        self.kl_fallbacks: List[str] = []     # the records the last kl_thresholds sent through kl_threshold
         self.reset_ranges()
 
     def _stream(self, stream=None):
@@ -746,6 +757,83 @@ class FloatStatsAccumulator:
         counts = self._download(self._digits, stream).view(np.uint64).reshape(self._n, DIGIT_BINS)
         return {n: counts[i, :used].copy() for i, n in enumerate(self.names)}
 
+    def kl_thresholds(self, num_quantized_bins: int = 255, stream=None) -> Dict[str, float]:
+        """{name: threshold} of relay.quantize's kl_divergence search over the accumulated
+        histograms, equal to ``kl_threshold``'s on each of them, with the search done where the
+        histograms lie (tk_kl_device): the device evaluates every candidate window as an interval
+        that contains the host's float32 divergence and lists the candidates that can be the host's
+        argmin; only those pick rows are downloaded.  A single survivor is the answer; several are
+        evaluated on the host by MinimizeKL's own code (tk_kl_candidates), first minimum wins.  A
+        record with more than KL_MAX_PICKS survivors or with no finite divergence goes through
+        ``kl_threshold`` (named in ``kl_fallbacks``); a count above INT32_MAX is a ValueError.
+        The pick rows stay in ``kl_picks``, the intervals are read by ``kl_table()``."""
+        import torch
+        from ..relay.quantize.passes import kl_threshold
+        self._live()
+        if self._hist is None:
+            raise ValueError("kl_thresholds: set_edges first")
+        bins, nq = self.bins, int(num_quantized_bins)
+        if bins % 2 == 0 or not 3 <= bins <= 8191 or not 2 <= nq <= bins:
+            raise ValueError(f"kl_thresholds: needs an odd number of bins in 3..8191 and 2..bins quantized bins, "
+                             f"not {bins} and {nq}")
+        n = len(self.names)
+        self._kl_cand = bins // 2 + 1 - nq // 2
+        self.kl_fallbacks = []
+        self.kl_picks = np.zeros(0, KL_PICK_DTYPE)
+        if not n:
+            return {}
+        dev = self.module.device
+        with torch.cuda.stream(self._stream(stream)):
+            self._kl_table = torch.empty(n * self._kl_cand * KL_ROW_DTYPE.itemsize // 8, dtype=torch.int64, device=dev)
+            picks_dev = torch.empty(n * KL_PICK_DTYPE.itemsize // 8, dtype=torch.int64, device=dev)
+        _lib.check(self.module.lib.tk_kl_device(
+            ctypes.c_void_p(self._hist.data_ptr()), n, bins, nq, ctypes.c_void_p(self._kl_table.data_ptr()),
+            ctypes.c_void_p(picks_dev.data_ptr()), self._handle(stream)), "tk_kl_device")
+        self.kl_picks = self._download(picks_dev, stream).view(KL_PICK_DTYPE).copy()
+        counts = None  # the histograms, read only if a record needs the host
+        found: Dict[str, float] = {}
+        for i, name in enumerate(self.names):
+            status, count = int(self.kl_picks[i]["status"]), int(self.kl_picks[i]["count"])
+            if status != KL_OK or count > 1:
+                if counts is None:
+                    counts = self._download(self._hist, stream).view(np.uint64).reshape(self._n, bins)
+                hist = counts[i]
+            if status == KL_COUNT_OVERFLOW:
+                raise ValueError(f"calibrate: a histogram bin of record {name} holds {int(hist.max())} values, "
+                                 "more than MinimizeKL's int32 counts take")
+            if status != KL_OK:
+                self.kl_fallbacks.append(name)
+                found[name] = kl_threshold(hist, self._edges_host[i], -1.0, "int8", bins, nq)
+                continue
+            idx = self.kl_picks[i]["idx"][:count]
+            k = int(idx[0])
+            if count > 1:  # the host's own evaluation of the survivors, ascending, strict <
+                rows = kl_candidates(hist, bins, nq, idx)
+                k = int(idx[int(np.argmin(rows["div"]))])
+            found[name] = float(self._edges_host[i][bins // 2 + nq // 2 + k + 1])
+        return found
+
+    def kl_table(self, stream=None) -> Dict[str, np.ndarray]:
+        """{name: KL_ROW_DTYPE rows, one per candidate} of the last ``kl_thresholds``: the device's
+        divergences, their bounds and the exact parts (for tests and diagnostics)."""
+        self._live()
+        if self._kl_table is None:
+            raise ValueError("kl_table: kl_thresholds first")
+        rows = self._download(self._kl_table, stream).view(KL_ROW_DTYPE).reshape(len(self.names), self._kl_cand)
+        return {n: rows[i].copy() for i, n in enumerate(self.names)}
+
     def close(self) -> None:
-        self._ranges = self._edges = self._hist = self._digits = self._prefix = None
+        self._ranges = self._edges = self._hist = self._digits = self._prefix = self._kl_table = None
         self._keep = []
+
+
+def kl_candidates(hist, num_bins: int, num_quantized_bins: int, cand) -> np.ndarray:
+    """tk_kl_candidates: MinimizeKL's own evaluation (KL_CANDIDATE_DTYPE rows) of the listed
+    candidates of one histogram of ``num_bins`` counts."""
+    h = np.ascontiguousarray(hist, np.int32)
+    c = np.ascontiguousarray(cand, np.int32)
+    out = np.zeros(c.size, KL_CANDIDATE_DTYPE)
+    _lib.check(_lib.load().tk_kl_candidates(h.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), num_bins,
+                                            num_quantized_bins, c.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), c.size,
+                                            ctypes.c_void_p(out.ctypes.data)), "tk_kl_candidates")
+    return out

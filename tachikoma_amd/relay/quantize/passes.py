@@ -545,7 +545,8 @@ def radix_select(count, ks) -> List[int]:
     return prefixes
 
 
-def device_scales(mod, dataset, mode: str, percentile: float = 0.99999, num_bins: int = 8001) -> List[float]:
+def device_scales(mod, dataset, mode: str, percentile: float = 0.99999, num_bins: int = 8001,
+                  device_kl: bool = False) -> List[float]:
     """The per-layer scales of ``collect_stats`` + ``find_scale_by_kl`` / ``find_scale_by_percentile``,
     equal to theirs, with the reductions done where the activations lie (tk_fstats.hip): the
     profile graph is built once, as ``collect_stats`` builds it, and run over the dataset
@@ -562,9 +563,16 @@ def device_scales(mod, dataset, mode: str, percentile: float = 0.99999, num_bins
     Deviations from the host path: a record with NaN or +-inf values raises a ValueError that names
     it in both modes (``find_scale_by_kl`` raises there too, from np.histogram's range check;
     ``find_scale_by_percentile`` does not), and a histogram count above INT32_MAX raises a
-    ValueError where the host path's int32 cast wraps."""
+    ValueError where the host path's int32 cast wraps.
+
+    ``device_kl`` (kl_divergence only) also searches the threshold on the device
+    (``FloatStatsAccumulator.kl_thresholds``, tk_kl.hip): the device brackets every candidate's
+    divergence, the host confirms the few that can be the minimum with MinimizeKL's own code, and
+    the thresholds are those of ``kl_threshold``."""
     if mode not in ("kl_divergence", "percentile"):
         raise ValueError(f"device_scales: mode must be kl_divergence or percentile, not {mode!r}")
+    if device_kl and mode != "kl_divergence":
+        raise ValueError(f"device_scales: device_kl needs the mode kl_divergence, not {mode!r}")
     from ..build_module import build
     from ...contrib.graph_executor import GraphModule
     dataset = list(dataset)
@@ -601,6 +609,9 @@ def device_scales(mod, dataset, mode: str, percentile: float = 0.99999, num_bins
                 refuse_nonfinite(name, ranges[name].nonfinite)
             acc.set_edges(num_bins)
             sweep(acc.add_histogram)
+            if device_kl:
+                found = acc.kl_thresholds(255)
+                return [found[name] for name in tnames]
             for name, (hist, edges) in acc.histograms().items():
                 if hist.size and int(hist.max()) > np.iinfo(np.int32).max:
                     raise ValueError(f"calibrate: a histogram bin of record {name} holds {int(hist.max())} values, "
@@ -623,26 +634,29 @@ def device_scales(mod, dataset, mode: str, percentile: float = 0.99999, num_bins
         gm.close()
 
 
-def _dataset_scales(mod, dataset, finder, device_stats: bool = False) -> List[float]:
+def _dataset_scales(mod, dataset, finder, device_stats: bool = False, device_kl: bool = False) -> List[float]:
     if dataset is None:
         raise ValueError("calibrate: this calibrate_mode needs a dataset (list of {input name: array})")
     cfg = current_qconfig()
     if device_stats:
-        return device_scales(mod, dataset, cfg.calibrate_mode)
+        return device_scales(mod, dataset, cfg.calibrate_mode, device_kl=device_kl)
     scales: List[float] = []
     for samples in collect_stats(mod, list(dataset), cfg.calibrate_chunk_by):
         scales += [finder(s) for s in samples]
     return scales
 
 
-def calibrate(mod, dataset=None, device_stats: bool = False) -> IRModule:
+def calibrate(mod, dataset=None, device_stats: bool = False, device_kl: bool = False) -> IRModule:
     """_calibrate.py:158-238 (``_set_params``): per simulated_quantize,
     dom_scale = scale / 2^(nbit - sign), clip = +-(2^(nbit - sign) - 1), all float32; the scale
     is ``global_scale``, or found on the dataset (``kl_divergence``, ``percentile``) for inputs and
     activations, and ``power2`` / ``max`` of the constant for weights.  With ``device_stats`` the
     dataset's scales come from ``device_scales`` (equal scales, no activation read back) instead
-    of ``collect_stats`` and the host finders."""
+    of ``collect_stats`` and the host finders; ``device_kl`` (with ``device_stats`` and
+    ``kl_divergence`` only, a ValueError otherwise) also searches the threshold there."""
     cfg = current_qconfig()
+    if device_kl and not (device_stats and cfg.calibrate_mode == "kl_divergence"):
+        raise ValueError("calibrate: device_kl needs device_stats=True and calibrate_mode kl_divergence")
     wfunc = {"power2": _power2_scale, "max": _max_scale}.get(cfg.weight_scale)
     if wfunc is None:
         raise ValueError(f"Unknown weight scale mode {cfg.weight_scale}")
@@ -650,7 +664,7 @@ def calibrate(mod, dataset=None, device_stats: bool = False) -> IRModule:
         dataset_scales = None
     elif cfg.calibrate_mode in ("kl_divergence", "percentile"):
         finder = find_scale_by_kl if cfg.calibrate_mode == "kl_divergence" else find_scale_by_percentile
-        found = _dataset_scales(mod, dataset, finder, device_stats)
+        found = _dataset_scales(mod, dataset, finder, device_stats, device_kl)
         n_act = len(stats_profile(mod)[1])
         if len(found) != n_act:
             raise RuntimeError(f"calibrate: {len(found)} profiled scales for {n_act} activation quantizers")
@@ -850,16 +864,19 @@ def realize(mod) -> IRModule:
 
 # ----------------------------------------------------------------------------- driver
 
-def quantize(mod, params=None, dataset=None, device_stats: bool = False) -> IRModule:
+def quantize(mod, params=None, dataset=None, device_stats: bool = False, device_kl: bool = False) -> IRModule:
     """quantize.py:330-379: prerequisite_optimize -> partition -> annotate -> calibrate ->
-    [realize] -> FoldConstant, under the current ``qconfig``.  ``device_stats``: see ``calibrate``."""
+    [realize] -> FoldConstant, under the current ``qconfig``.  ``device_stats``, ``device_kl``: see
+    ``calibrate``."""
     cfg = current_qconfig()
+    if device_kl and not (device_stats and cfg.calibrate_mode == "kl_divergence"):
+        raise ValueError("quantize: device_kl needs device_stats=True and calibrate_mode kl_divergence")
     if cfg.partition_conversions not in ("disabled", "enabled", "fully_integral"):
         raise ValueError(f"partition_conversions={cfg.partition_conversions!r}")
     mod = prerequisite_optimize(mod, params)
     mod = partition(mod)
     mod = annotate(mod, _QuantizeContext())
-    mod = calibrate(mod, dataset, device_stats)
+    mod = calibrate(mod, dataset, device_stats, device_kl)
     if not cfg.do_simulation:
         mod = realize(mod)
     mod = fold_constant(mod)

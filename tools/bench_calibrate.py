@@ -18,8 +18,16 @@ and "whole-lane add", each in a process of its own on the profiling build of the
 (tachikoma_amd/build.py --ablation, TK_FSTATS_REMEDY; the product library has the zeros in
 registers only, which is what this A/B kept).
 
+--device-kl measures the threshold search on the device (device_scales(..., device_kl=True),
+csrc/tk_kl.hip) against the device_stats=True path of the parent commit, whose tree --parent-tree
+names (an export of that commit with its library built): interleaved child processes, one per
+tree, each one warm-up call and --rounds timed ones.  Then, on this tree, the evaluate and the
+select kernel from HIP events over the histograms of the profile graph, the survivors per layer,
+the fallbacks and the largest part of the bound that the host's divergences use.
+
     python tools/bench_calibrate.py --out profiles/device_calibration_resnet18.json
-    python tools/bench_calibrate.py --remedy --out profiles/device_calibration_remedy.json"""
+    python tools/bench_calibrate.py --remedy --out profiles/device_calibration_remedy.json
+    python tools/bench_calibrate.py --device-kl --parent-tree DIR --out profiles/device_kl_resnet18.json"""
 from __future__ import annotations
 
 import argparse
@@ -206,6 +214,115 @@ def remedy(args) -> dict:
                              "zero_fraction": v[0]["zero_fraction"], "rounds": v} for k, v in rows.items()}}
 
 
+def child_e2e(args) -> dict:
+    """kl_divergence scales of one variant, in the tree this process imports: one warm-up call and
+    args.rounds timed ones."""
+    import numpy as np
+    from tachikoma_amd import _lib, zoo
+    from tachikoma_amd.relay.quantize import passes, qconfig
+    m = zoo.resnet_float(args.depth, batch=args.batch, hw=args.hw)
+    mod = _annotated(m)
+    data = [{"data": m.random_input(seed=s)} for s in range(args.batches)]
+    kw = {"device_kl": True} if args.child_e2e == "device_kl" else {}
+    wall, scales = [], None
+    with qconfig(calibrate_mode="kl_divergence"):
+        for rnd in range(args.rounds + 1):
+            t0 = time.perf_counter()
+            scales = passes.device_scales(mod, data, "kl_divergence", **kw)
+            if rnd:
+                wall.append(time.perf_counter() - t0)
+    return {"variant": args.child_e2e, "library": _lib.build_info(), "wall_s": wall, "layers": len(scales),
+            "scales_hex": np.array(scales, np.float64).tobytes().hex()}
+
+
+def kl_kernels(args) -> dict:
+    """The two kernels of tk_kl_device over the histograms of the profile graph (HIP events), and
+    what the search came to per layer against the host's own divergences."""
+    import numpy as np
+    import torch
+    from tachikoma_amd import _lib, relay, zoo
+    from tachikoma_amd.contrib import graph_executor, trace_device
+    from tachikoma_amd.relay.quantize import passes
+
+    m = zoo.resnet_float(args.depth, batch=args.batch, hw=args.hw)
+    mod = _annotated(m)
+    prof, targets = passes.stats_profile(mod)
+    gm = graph_executor.GraphModule(relay.build(prof, target="mi355x")["default"]())
+    try:
+        names, counter = {}, 0
+        for n in relay.post_order(prof["main"].body):
+            if isinstance(n, relay.Call):
+                names[id(n)] = f"%{counter}"
+                counter += 1
+            elif isinstance(n, relay.Var):
+                names[id(n)] = n.name_hint
+        uniq = list(dict.fromkeys(names[id(t)] for t in targets))
+        acc = gm.float_stats_accumulator(uniq)
+        data = [m.random_input(seed=s) for s in range(args.batches)]
+        for x in data:
+            gm.run(data=x)
+            acc.add_range()
+        acc.set_edges(8001)
+        for x in data:
+            gm.run(data=x)
+            acc.add_histogram()
+        bins, nq = 8001, 255
+        t0 = time.perf_counter()
+        found = acc.kl_thresholds(nq)
+        search_s = time.perf_counter() - t0
+        picks, table = acc.kl_picks, acc.kl_table()
+        lib, n = gm.module.lib, len(uniq)
+        s = ctypes.c_void_p(_lib.stream_handle(None))
+        hist, tab = ctypes.c_void_p(acc._hist.data_ptr()), ctypes.c_void_p(acc._kl_table.data_ptr())
+        pk = torch.empty(n * trace_device.KL_PICK_DTYPE.itemsize // 8, dtype=torch.int64, device=gm.module.device)
+        steps = {"evaluate": lambda: _lib.check(lib.tk_kl_device_evaluate(hist, n, bins, nq, tab, s), "evaluate"),
+                 "select": lambda: _lib.check(lib.tk_kl_device_select(hist, n, bins, nq, tab, ctypes.c_void_p(pk.data_ptr()), s),
+                                              "select")}
+        ms = {k: [_timed(fn) for _ in range(REPS)] for k, fn in steps.items()}
+        counts = acc.histograms()
+        used, host_s, equal = 0.0, 0.0, True
+        for name in uniq:
+            h, edges = counts[name]
+            t0 = time.perf_counter()
+            host = trace_device.kl_candidates(h, bins, nq, np.arange(table[name].size))
+            host_s += time.perf_counter() - t0
+            fin = np.isfinite(host["div"])
+            err = np.abs(host["div"][fin].astype(np.float64) - table[name]["d"][fin])
+            used = max(used, float((err / table[name]["bound"][fin]).max()))
+            want = float(edges[bins // 2 + nq // 2 + int(np.argmin(host["div"])) + 1])
+            equal = equal and np.float32(want).tobytes() == np.float32(found[name]).tobytes()
+        return {"layers": n, "bins": bins, "quantized_bins": nq, "candidates_per_layer": int(table[uniq[0]].size),
+                "evaluate_ms": _spread(ms["evaluate"]), "select_ms": _spread(ms["select"]),
+                "kl_thresholds_wall_s": round(search_s, 4), "host_all_candidates_s": round(host_s, 3),
+                "survivors_per_layer": [int(c) for c in picks["count"]], "statuses": [int(c) for c in picks["status"]],
+                "fallbacks": len(acc.kl_fallbacks), "largest_bound_fraction_used": round(used, 4),
+                "thresholds_equal_host_argmin": bool(equal)}
+    finally:
+        gm.close()
+
+
+def device_kl(args) -> dict:
+    script = os.path.abspath(__file__)
+    trees = {"device_stats_parent": (args.parent_tree, "device"), "device_kl": (ROOT, "device_kl")}
+    rows = {k: [] for k in trees}
+    for _ in range(2):  # interleaved: parent, this tree, parent, this tree
+        for name, (tree, variant) in trees.items():
+            r = subprocess.run([sys.executable, script, "--child-e2e", variant, "--tree", tree, "--depth", str(args.depth),
+                                "--batch", str(args.batch), "--hw", str(args.hw), "--batches", str(args.batches),
+                                "--rounds", str(args.rounds)], stdout=subprocess.PIPE, text=True, check=True, timeout=600)
+            rows[name].append(json.loads(next(ln for ln in r.stdout.splitlines() if ln.startswith("RESULT "))[7:]))
+            print(f"[bench_calibrate] {name}: {rows[name][-1]['wall_s']}", file=sys.stderr, flush=True)
+    out = {}
+    for name, rs in rows.items():
+        wall = [w for r in rs for w in r["wall_s"]]
+        out[name] = {"library": rs[0]["library"], "wall_s": [round(w, 3) for w in wall], "wall_s_spread": _spread(wall),
+                     "layers": rs[0]["layers"]}
+    out["scales_equal"] = len({r["scales_hex"] for rs in rows.values() for r in rs}) == 1
+    out["parent_over_device_kl"] = round(out["device_stats_parent"]["wall_s_spread"]["median"] /
+                                         out["device_kl"]["wall_s_spread"]["median"], 3)
+    return out
+
+
 def main() -> int:
     p = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     p.add_argument("--depth", type=int, default=18)
@@ -216,12 +333,26 @@ def main() -> int:
     p.add_argument("--elements", default=str(1 << 26), help="--remedy: float32 elements of the synthetic record")
     p.add_argument("--remedy", action="store_true")
     p.add_argument("--child-remedy", action="store_true")
+    p.add_argument("--device-kl", action="store_true")
+    p.add_argument("--parent-tree", default=None, help="--device-kl: the parent commit's tree, library built")
+    p.add_argument("--child-e2e", default=None, choices=["device", "device_kl"])
+    p.add_argument("--tree", default=None, help="--child-e2e: the tree to import tachikoma_amd from")
     p.add_argument("--out", default=None)
     args = p.parse_args()
+    if args.child_e2e:
+        sys.path.insert(0, os.path.abspath(args.tree or ROOT))
+        print("RESULT " + json.dumps(child_e2e(args)), flush=True)
+        return 0
     if args.child_remedy:
         print("RESULT " + json.dumps(child_remedy(args)), flush=True)
         return 0
-    if args.remedy:
+    if args.device_kl:
+        if not args.parent_tree:
+            p.error("--device-kl needs --parent-tree")
+        out = {"model": f"resnet{args.depth}_float", "batch": args.batch, "hw": args.hw, "dataset_batches": args.batches,
+               "rounds_per_process": args.rounds, "end_to_end_kl_divergence": device_kl(args), "kernels": kl_kernels(args),
+               "counter_run": False}
+    elif args.remedy:
         out = {"contention_remedy": remedy(args)}
     else:
         out = {"model": f"resnet{args.depth}_float", "batch": args.batch, "hw": args.hw, "dataset_batches": args.batches,
