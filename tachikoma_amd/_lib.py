@@ -374,6 +374,8 @@ class tk_array_meta(ctypes.Structure):
 # ---------------------------------------------------------------- constants
 TK_DL_INT, TK_DL_UINT, TK_DL_FLOAT = 0, 1, 2
 TK_DEV_CPU, TK_DEV_ROCM = 1, 10
+(TK_ERR_INVALID_ARG, TK_ERR_UNSUPPORTED, TK_ERR_SHAPE, TK_ERR_DTYPE, TK_ERR_HIP, TK_ERR_IO,
+ TK_ERR_FORMAT) = range(-1, -8, -1)
 TK_ROUND_UPWARD, TK_ROUND_TONEAREST = 0, 1
 (TK_RQ_IDENTITY, TK_RQ_TENSOR_POW2, TK_RQ_TENSOR_UPWARD, TK_RQ_TENSOR_TONEAREST, TK_RQ_AXIS_UPWARD,
  TK_RQ_AXIS_TONEAREST) = range(6)
