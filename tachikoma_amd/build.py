@@ -32,7 +32,7 @@ ARCH = "gfx950"
 
 SOURCES = ["tk_host.cc", "tk_calibrate.cc", "tk_format.cc", "tk_wire.cc", "tk_capture_plan.cc", "tk_capture.cc", "tk_runtime.cc", "tk_elementwise.hip", "tk_trace.hip", "tk_shadow.hip", "tk_chain.hip", "tk_stats.hip", "tk_fstats.hip", "tk_kl.hip",
            "tk_gemm.hip", "tk_residual.hip", "tk_realize.hip", "tk_conv_img.hip", "tk_conv_pf.hip", "tk_qnn_ops.hip", "tk_dense.hip", "tk_dw.hip"]
-HEADERS = ["tk_common.h", "tk_tensor.h", "tk_node.h", "tk_ops.h", "tk_module.h", "tk_capture_plan.h", "tk_conv.h", "tk_wire.h",
+HEADERS = ["tk_common.h", "tk_tensor.h", "tk_node.h", "tk_ops.h", "tk_module.h", "tk_capture_plan.h", "tk_conv.h", "tk_block_tail.h", "tk_wire.h",
            "tk_chain.h", "tk_fstats.h", "tk_kl.h"]
 BASE_FLAGS = ["-std=c++20", "-O3", "-fPIC", "-fvisibility=hidden", f"--offload-arch={ARCH}", "-Wall",
               "-Wno-unused-function"]

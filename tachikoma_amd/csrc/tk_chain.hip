@@ -5,7 +5,7 @@
 // elementwise over records that are all there: bias_add of the conv record, requantize of the
 // bias_add record, qnn.add of the requantize record and the residual, clip of its predecessor.
 // This kernel computes each of them with the fused epilogues' own device functions (rq_apply and
-// the qms_* forms of tk_common.h, the 256-entry RequantizeOrUpcast tables of tk_residual.hip) and
+// the qms_* forms of tk_common.h, the 256-entry RequantizeOrUpcast tables of tk_block_tail.h) and
 // compares with the recorded output.  It stores nothing into a record.
 //
 // One launch takes every chain of a table.  A workgroup finds its chain by binary search over the
@@ -26,6 +26,7 @@
 #include <string>
 #include <vector>
 
+#include "tk_block_tail.h"
 #include "tk_chain.h"
 #include "tk_wire.h"
 
@@ -57,10 +58,7 @@ __global__ __launch_bounds__(256) void chain_check_kernel(const ChainDev* __rest
   const bool is_u8 = ch.is_u8, has_i32 = ch.has_i32, has_add = ch.has_add, has_clip = ch.has_clip;
   const int32_t qmin = is_u8 ? 0 : -128, qmax = is_u8 ? 255 : 127;
   if (has_add) {
-    // as tk_residual.hip tabulates them (op_common.h:186-200)
-    const int32_t x = is_u8 ? tid : (int32_t)(int8_t)(uint8_t)tid;
-    lut[tid] = ch.add_up_b ? x : rq_apply(x, 0, ch.add_pb);
-    lut[256 + tid] = ch.add_up_r ? x : rq_apply(x, 0, ch.add_pr);
+    block_join_lut(tid, lut, is_u8, ch.add_up_b, ch.add_up_r, ch.add_pb, ch.add_pr);
     __syncthreads();
   }
   const int64_t n = ch.n;

@@ -1,10 +1,13 @@
-// Definitions shared by the MFMA conv-block kernels (tk_gemm.hip: im2col / patch kernels and
-// the host dispatch; tk_conv_img.hip: image-tile kernel): kernel arguments, the fused block
-// epilogue's per-row constants, device helpers and the host-side conv geometry.
+// Definitions shared by the conv / dense block kernels (tk_gemm.hip: im2col, patch, direct and
+// band kernels and the host dispatch; tk_conv_img.hip: image-tile kernel; tk_conv_pf.hip:
+// persistent im2col kernel; tk_dw.hip: depthwise tile kernel; tk_dense.hip: small-batch dense
+// tiles): kernel arguments, the fused block epilogue's per-row constants, device helpers and the
+// host-side conv geometry.  The block tail's arithmetic is tk_block_tail.h.
 #pragma once
 
 #include <cstdlib>
 
+#include "tk_block_tail.h"
 #include "tk_common.h"
 
 namespace tk {
@@ -99,18 +102,6 @@ struct EpiRow {
 };
 
 
-// requantize core of one element (mode is uniform; used where constants vary per element)
-__device__ __forceinline__ int32_t rq_core(int32_t t, int mode, int32_t m, int32_t sh) {
-  switch (mode) {
-    case TK_RQ_IDENTITY: return t;
-    case TK_RQ_TENSOR_POW2: return qms_pow2(t, sh);
-    case TK_RQ_TENSOR_TONEAREST:
-    case TK_RQ_AXIS_TONEAREST: return qms_tonearest(t, m, sh);
-    default: return qms_upward(t, m, sh);
-  }
-}
-
-
 // 16-byte rows of every byte value: the LDS-DMA source of out-of-bounds im2col taps
 // (the input zero point) and of padding rows (0); constant-initialised in device memory.
 struct FillRows {
@@ -147,19 +138,6 @@ __device__ __forceinline__ T ldg(const T* p) {
 }
 
 
-// per-tensor requantize core (no per-channel arrays): the qnn.add operand tables
-__device__ __forceinline__ int32_t rq_tensor(int32_t t, const RqParams& p) {
-  t = (int32_t)((uint32_t)t - (uint32_t)p.zp_in);
-  switch (p.mode) {
-    case TK_RQ_TENSOR_POW2: t = qms_pow2(t, p.shift); break;
-    case TK_RQ_TENSOR_UPWARD: t = qms_upward(t, p.multiplier, p.shift); break;
-    case TK_RQ_TENSOR_TONEAREST: t = qms_tonearest(t, p.multiplier, p.shift); break;
-    default: break;
-  }
-  return (int32_t)((uint32_t)p.zp_out + (uint32_t)t);
-}
-
-
 // ---- fast conv-block epilogue helpers
 // buffer descriptor of a record (uniform base and size): stores at offsets >= bytes are
 // dropped by the range check, which masks the tile edges without branches
@@ -168,21 +146,6 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t rec_rsrc(const void* base, uin
 }
 constexpr int kAuxNT = 2;  // cache policy: nontemporal
 constexpr uint32_t kOffDrop = 0x3FFFFFF0u;  // element offset of a masked lane (x4 + 15 stays out of range)
-
-__device__ __forceinline__ uint32_t pack4u(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
-  // low bytes of a, b, c, d -> one dword (two v_perm_b32 + v_or)
-  const uint32_t lo = __builtin_amdgcn_perm(b, a, 0x0c0c0400u);
-  const uint32_t hi = __builtin_amdgcn_perm(d, c, 0x04000c0cu);
-  return lo | hi;
-}
-
-// min(max(x, lo), hi) in one v_med3_i32 (the compiler only forms it for constant bounds); needs
-// lo <= hi, which setup_block guarantees for the clip bounds (see there) and the dtype ranges are
-__device__ __forceinline__ int32_t clamp_i32(int32_t x, int32_t lo, int32_t hi) {
-  int32_t r;
-  asm("v_med3_i32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "v"(lo), "v"(hi));
-  return r;
-}
 
 // counted wait for this wave's global loads (vmcnt immediate): at most n outstanding
 __device__ __forceinline__ void wait_vm(int n) {

@@ -447,17 +447,11 @@ __global__ __launch_bounds__(kGemmThreads, 2) void conv_img_kernel(GemmArgs g, I
     if (!rq_axis) r.m = g.rq.multiplier, r.s = g.rq.shift;
     if (!g.rq.zps) r.zp = g.rq.zp_in;
     r.fold = (uint32_t)0 - (uint32_t)g.zB * r.ra;  // weights' zero point 0: the fold is -za * rowsum
-    if (r.s > -2) s_fast = 0;
+    if (!block_rq_fast_shift(r.s)) s_fast = 0;
     rowc[tid] = r;
   }
   if (has_add) {
-    // RequantizeOrUpcast of every 8-bit value of both qnn.add operands (op_common.h:186-200): the
-    // block's own values indexed by value - qmin (one v_lshl_add per lookup), the residual's by its
-    // raw byte, with the add's - zp_out folded in
-    const int32_t xb = (int32_t)g.rq.qmin + tid;
-    const int32_t xr = g.rq.qmin == 0 ? tid : (int32_t)(int8_t)(uint8_t)tid;
-    lut[tid] = g.add_up_b ? xb : rq_tensor(xb, g.add_pb);
-    lut[256 + tid] = (int32_t)((uint32_t)(g.add_up_r ? xr : rq_tensor(xr, g.add_pr)) - (uint32_t)g.add_zp);
+    block_join_lut_folded(tid, lut, (int32_t)g.rq.qmin, g.add_up_b, g.add_up_r, g.add_pb, g.add_pr, g.add_zp);
   }
   const int ts = h.tstride;
   // columns of the tile staged per pass: [c0, c0 + span)
@@ -494,7 +488,6 @@ __global__ __launch_bounds__(kGemmThreads, 2) void conv_img_kernel(GemmArgs g, I
   // for each pixel / row wrap (no per-group products)
   const uint32_t dO = (uint32_t)(dr * hw + dp), dOp = (uint32_t)(hw - W), dOr = (uint32_t)((Mrows - R) * hw);
   const int dB = dr * ts + dp, dBp = ts - W, dBr = W - R * ts;
-  const int32_t* lut_b = lut - (int32_t)g.rq.qmin;  // lut_b[q], q in [qmin, qmin + 255]
   const int tile_end = R * ts;  // staging words (a group's reads are clamped below it)
   int c0 = 0;  // first pixel of the current pass
   // nontemporal record stores (plain ones measured no faster, also on multi-pass epilogues:
@@ -584,31 +577,19 @@ __global__ __launch_bounds__(kGemmThreads, 2) void conv_img_kernel(GemmArgs g, I
       if (!TK_ABL(2)) st128(v, r_bias, o * 4u);
       int32_t q[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int32_t t = (int32_t)(v[e] - zp[e]);
-        int32_t y;
-        if constexpr (FAST) {
-          // right shift >= 2: (x·m + 2^(30+rs)) >> (31+rs) only needs the high word of x·m
-          const int sh2 = -sh[e] - 1;
-          y = (int32_t)((uint32_t)__mulhi(t, m[e]) + (1u << (sh2 - 1))) >> sh2;
-        } else {
-          y = rq_core(t, mode, m[e], sh[e]);
-        }
-        q[e] = clamp_i32((int32_t)((uint32_t)zpo + (uint32_t)y), qmin, qmax);
-      }
+      for (int e = 0; e < 4; ++e) q[e] = block_rq<FAST>(v[e], zp[e], m[e], sh[e], mode, zpo, qmin, qmax);
       if (!TK_ABL(2)) st32(pack4u(q[0], q[1], q[2], q[3]), r_rq, o);
       if constexpr (ADD) {
-        // qnn.add (src/relay/qnn/op/add.cc:40-96): RQ(block) + RQ(residual) - zp_out
 #pragma unroll
-        for (int e = 0; e < 4; ++e)
-          q[e] = clamp_i32(TK_ABL(8192) ? q[e] + (int32_t)((res >> (8 * e)) & 0xFFu) - add_zp
-                                        : (int32_t)((uint32_t)lut_b[q[e]] + (uint32_t)lut[256 + ((res >> (8 * e)) & 0xFFu)]),
-                           qmin, qmax);
+        for (int e = 0; e < 4; ++e) {
+          const uint32_t rb = (res >> (8 * e)) & 0xFFu;
+          q[e] = TK_ABL(8192) ? clamp_i32(q[e] + (int32_t)rb - add_zp, qmin, qmax) : block_join<true>(q[e], rb, lut, add_zp, qmin, qmax);
+        }
         if (!TK_ABL(16384 | 2)) st32(pack4u(q[0], q[1], q[2], q[3]), r_add, o);
       }
       if constexpr (CLIP) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) q[e] = clamp_i32(q[e], clip_lo, clip_hi);
+        for (int e = 0; e < 4; ++e) q[e] = block_clip(q[e], clip_lo, clip_hi);
         if (!TK_ABL(2)) st32(pack4u(q[0], q[1], q[2], q[3]), r_clip, o);
       }
       if constexpr (ROWU) {
@@ -645,7 +626,7 @@ __global__ __launch_bounds__(kGemmThreads, 2) void conv_img_kernel(GemmArgs g, I
       __builtin_amdgcn_s_waitcnt(0x0F70);
     }
     lds_barrier();  // (also publishes s_fast and the row constants)
-    if (s_fast && (mode == TK_RQ_AXIS_UPWARD || mode == TK_RQ_TENSOR_UPWARD)) by_add(T{});
+    if (s_fast && block_rq_fast_mode(mode)) by_add(T{});
     else by_add(F{});
 
     // ---- the next conv's shadow: 16 channels of one pixel per 16-byte store; the pass's columns

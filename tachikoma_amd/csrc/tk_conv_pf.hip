@@ -93,10 +93,7 @@ __global__ __launch_bounds__(kGemmThreads, kRing == 2 ? 2 : 1) void conv_pf_kern
   constexpr int kStoresPerTile = kRows * (3 + (ADD ? 1 : 0) + (CLIP ? 1 : 0)) + (SHADOW ? 2 : 0);
 
   if (ADD) {
-    // RequantizeOrUpcast of every 8-bit value of both qnn.add operands (op_common.h:186-200)
-    const int32_t x = g.rq.qmin == 0 ? tid : (int32_t)(int8_t)(uint8_t)tid;
-    lut[tid] = g.add_up_b ? x : rq_tensor(x, g.add_pb);
-    lut[256 + tid] = g.add_up_r ? x : rq_tensor(x, g.add_pr);
+    block_join_lut(tid, lut, g.rq.qmin == 0, g.add_up_b, g.add_up_r, g.add_pb, g.add_pr);
   }
 
   // ---- tile order: tile_of (tk_gemm.hip) for virtual workgroup L; padding tiles are skipped
@@ -279,7 +276,8 @@ __global__ __launch_bounds__(kGemmThreads, kRing == 2 ? 2 : 1) void conv_pf_kern
       r.zp = g.rq.zps ? raw[256 + lane] : g.rq.zp_in;
       r.fold = fold_k - (uint32_t)g.zB * r.ra;
       rowc[lane] = r;
-      const bool fast = __builtin_amdgcn_ballot_w64(r.s > -2) == 0;
+      // (the mode is an UPWARD one: conv_pf_applies asks for fast_epi)
+      const bool fast = __builtin_amdgcn_ballot_w64(!block_rq_fast_shift(r.s)) == 0;
       if (lane == 0) s_fast = fast ? 1 : 0;
     }
     uint32_t res[kRows];
@@ -317,29 +315,17 @@ __global__ __launch_bounds__(kGemmThreads, kRing == 2 ? 2 : 1) void conv_pf_kern
         v += (uint32_t)r.bias;
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i, v), r_bias, o * 4u, 0, AUX);
         int32_t q[4];
-        if constexpr (FAST) {
-          const int sh2 = -r.s - 1;
-          const uint32_t rnd = 1u << (sh2 - 1);
 #pragma unroll
-          for (int e = 0; e < 4; ++e)
-            q[e] = clamp_i32(zpo + ((int32_t)((uint32_t)__mulhi((int32_t)(v[e] - (uint32_t)r.zp), r.m) + rnd) >> sh2),
-                             qmin, qmax);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            q[e] = clamp_i32((int32_t)((uint32_t)zpo + (uint32_t)rq_core((int32_t)(v[e] - (uint32_t)r.zp), mode, r.m, r.s)),
-                             qmin, qmax);
-        }
+        for (int e = 0; e < 4; ++e) q[e] = block_rq<FAST>(v[e], (uint32_t)r.zp, r.m, r.s, mode, zpo, qmin, qmax);
         __builtin_amdgcn_raw_buffer_store_b32(pack4u(q[0], q[1], q[2], q[3]), r_rq, o, 0, AUX);
         if (ADD) {
 #pragma unroll
-          for (int e = 0; e < 4; ++e)
-            q[e] = clamp_i32(lut[q[e] & 0xFF] + lut[256 + ((res[k] >> (8 * e)) & 0xFFu)] - add_zp, qmin, qmax);
+          for (int e = 0; e < 4; ++e) q[e] = block_join(q[e], (res[k] >> (8 * e)) & 0xFFu, lut, add_zp, qmin, qmax);
           __builtin_amdgcn_raw_buffer_store_b32(pack4u(q[0], q[1], q[2], q[3]), r_add, o, 0, AUX);
         }
         if (CLIP) {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) q[e] = clamp_i32(q[e], clip_lo, clip_hi);
+          for (int e = 0; e < 4; ++e) q[e] = block_clip(q[e], clip_lo, clip_hi);
           __builtin_amdgcn_raw_buffer_store_b32(pack4u(q[0], q[1], q[2], q[3]), r_clip, o, 0, AUX);
         }
         if (SHADOW) *reinterpret_cast<v4i*>(slot) = v4i{q[0], q[1], q[2], q[3]};

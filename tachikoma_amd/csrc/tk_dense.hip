@@ -45,8 +45,7 @@ __device__ __forceinline__ void dense_epilogue(const GemmArgs& g, int b, int u0,
   };
   auto put8 = [&](uint8_t* dst, const int32_t* w) {
     if (full) {  // (4-aligned in a [B, U] record: one dword)
-      *reinterpret_cast<uint32_t*>(dst + off) = ((uint32_t)w[0] & 0xFFu) | (((uint32_t)w[1] & 0xFFu) << 8) |
-                                                (((uint32_t)w[2] & 0xFFu) << 16) | ((uint32_t)w[3] << 24);
+      *reinterpret_cast<uint32_t*>(dst + off) = pack4u(w[0], w[1], w[2], w[3]);
     } else {
       for (int e = 0; e < 4; ++e)
         if (u0 + e < g.M) dst[off + e] = (uint8_t)w[e];
@@ -54,18 +53,21 @@ __device__ __forceinline__ void dense_epilogue(const GemmArgs& g, int b, int u0,
   };
   put32(g.C, v);
   if (!g.bias_out) return;  // a plain contraction (no block)
-#pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = (int32_t)((uint32_t)v[e] + (uint32_t)g.bias[min(u0 + e, g.M - 1)]);
-  put32(g.bias_out, v);
+  BlockConsts k[4];
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    const int32_t q = rq_apply(v[e], min(u0 + e, g.M - 1), g.rq);
-    v[e] = (int32_t)min(max((int64_t)q, g.rq.qmin), g.rq.qmax);
+    k[e] = block_consts(g.bias, g.rq, min(u0 + e, g.M - 1));
+    v[e] = (int32_t)((uint32_t)v[e] + (uint32_t)k[e].bias);
   }
+  put32(g.bias_out, v);
+#pragma unroll
+  for (int e = 0; e < 4; ++e)
+    v[e] = block_rq<false>((uint32_t)v[e], (uint32_t)k[e].zp, k[e].m, k[e].s, g.rq.mode, g.rq.zp_out, (int32_t)g.rq.qmin,
+                           (int32_t)g.rq.qmax);
   put8(g.rq_out, v);
   if (g.has_clip) {
 #pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = min(max(v[e], g.clip_lo), g.clip_hi);
+    for (int e = 0; e < 4; ++e) v[e] = block_clip(v[e], g.clip_lo, g.clip_hi);
     put8(g.clip_out, v);
   }
   if (g.shadow_out) {

@@ -97,22 +97,11 @@ __device__ __forceinline__ void dw_epilogue(const GemmArgs& g, const DwConst* cs
   __builtin_amdgcn_raw_buffer_store_b128(v4i{v[0], v[1], v[2], v[3]}, r_bias, o * 4u, 0, 0);
   int32_t q[4];
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int32_t t = (int32_t)((uint32_t)v[e] - (uint32_t)k[e].zp);
-    int32_t y;
-    if constexpr (FAST) {
-      // right shift >= 2: (x·m + 2^(30+rs)) >> (31+rs) only needs the high word of x·m
-      const int sh2 = -k[e].s - 1;
-      y = (int32_t)((uint32_t)__mulhi(t, k[e].m) + (1u << (sh2 - 1))) >> sh2;
-    } else {
-      y = rq_core(t, mode, k[e].m, k[e].s);
-    }
-    q[e] = clamp_i32((int32_t)((uint32_t)zpo + (uint32_t)y), qmin, qmax);
-  }
+  for (int e = 0; e < 4; ++e) q[e] = block_rq<FAST>((uint32_t)v[e], (uint32_t)k[e].zp, k[e].m, k[e].s, mode, zpo, qmin, qmax);
   __builtin_amdgcn_raw_buffer_store_b32(pack4u(q[0], q[1], q[2], q[3]), r_rq, o, 0, 0);
   if (clip) {
 #pragma unroll
-    for (int e = 0; e < 4; ++e) q[e] = clamp_i32(q[e], g.clip_lo, g.clip_hi);
+    for (int e = 0; e < 4; ++e) q[e] = block_clip(q[e], g.clip_lo, g.clip_hi);
     __builtin_amdgcn_raw_buffer_store_b32(pack4u(q[0], q[1], q[2], q[3]), r_clip, o, 0, 0);
   }
   if (shadow) {

@@ -34,14 +34,14 @@ template <bool kBlock>
 __device__ __forceinline__ void epilogue_store(const GemmArgs& g, int64_t off, int ch, int64_t pix, uint32_t v) {
   g.C[off] = (int32_t)v;
   if (!kBlock) return;
-  int32_t b = (int32_t)(v + (uint32_t)g.bias[ch]);
-  g.bias_out[off] = b;
-  int32_t q = rq_apply(b, ch, g.rq);
-  q = (int32_t)min(max((int64_t)q, g.rq.qmin), g.rq.qmax);
+  const BlockConsts c = block_consts(g.bias, g.rq, ch);
+  v += (uint32_t)c.bias;
+  g.bias_out[off] = (int32_t)v;
+  const int32_t q = block_rq<false>(v, (uint32_t)c.zp, c.m, c.s, g.rq.mode, g.rq.zp_out, (int32_t)g.rq.qmin, (int32_t)g.rq.qmax);
   g.rq_out[off] = (uint8_t)q;
   int32_t last = q;
   if (g.has_clip) {
-    last = min(max(q, g.clip_lo), g.clip_hi);
+    last = block_clip(q, g.clip_lo, g.clip_hi);
     g.clip_out[off] = (uint8_t)last;
   }
   if (g.shadow_out) {
@@ -50,12 +50,6 @@ __device__ __forceinline__ void epilogue_store(const GemmArgs& g, int64_t off, i
       for (int c2 = ch + 1; c2 < g.shadow_cpad; ++c2) g.shadow_out[((int64_t)(c2 >> 4) * g.N + pix) * 16 + (c2 & 15)] = 0;
   }
 }
-
-__device__ __forceinline__ uint32_t pack4(const int32_t* x) {
-  return (uint32_t)(x[0] & 0xFF) | ((uint32_t)(x[1] & 0xFF) << 8) | ((uint32_t)(x[2] & 0xFF) << 16) |
-         ((uint32_t)x[3] << 24);
-}
-
 
 // record stores (nontemporal: see store_nt in tk_common.h)
 template <int V>
@@ -71,8 +65,9 @@ __device__ __forceinline__ void st_i32(int32_t* dst, const int32_t* v, bool nt) 
 template <int V>
 __device__ __forceinline__ void st_i8(uint8_t* dst, const int32_t* v, bool nt) {
   if constexpr (V == 4) {
-    if (nt) __builtin_nontemporal_store(pack4(v), reinterpret_cast<uint32_t*>(dst));
-    else *reinterpret_cast<uint32_t*>(dst) = pack4(v);
+    const uint32_t w = pack4u(v[0], v[1], v[2], v[3]);
+    if (nt) __builtin_nontemporal_store(w, reinterpret_cast<uint32_t*>(dst));
+    else *reinterpret_cast<uint32_t*>(dst) = w;
   } else {
     *dst = (uint8_t)v[0];
   }
@@ -80,84 +75,37 @@ __device__ __forceinline__ void st_i8(uint8_t* dst, const int32_t* v, bool nt) {
 
 // V consecutive columns of one row after zero-point folding: stores each record as
 // soon as it is complete, transforming v in place (conv → bias_add → requantize →
-// clip); mirrors nn.bias_add (int32 wrap), RequantizeLowerInt + clip/cast
-// (src/relay/qnn/op/requantize.cc:195-273) and clip (python/tvm/topi/math.py:615-640).
-
-// Column constants of a dense block (channel = column), loaded once per thread.
-__device__ __forceinline__ EpiRow col_consts(const GemmArgs& g, int col) {
-  EpiRow c{};
-  const int ch = min(col, g.N - 1);
-  c.bias = g.bias[ch];
-  const bool axis = g.rq.mode >= TK_RQ_AXIS_UPWARD;
-  c.m = axis ? g.rq.ms[ch] : g.rq.multiplier;
-  c.s = axis ? g.rq.ss[ch] : g.rq.shift;
-  c.zp = g.rq.zps ? g.rq.zps[ch] : g.rq.zp_in;
-  return c;
-}
-
+// [qnn.add] → [clip], tk_block_tail.h).  The channel is the row (conv blocks: constants r)
+// or the column (dense blocks: constants cc[q], loaded once per thread with block_consts).
 template <int V, bool kBlock>
 __device__ __forceinline__ void epi_apply(const GemmArgs& g, const EpiRow& r, int32_t* v, int64_t off, bool st,
-                                          int col, uint32_t resid, const int32_t* lut, const EpiRow* cc) {
+                                          int col, uint32_t resid, const int32_t* lut, const BlockConsts* cc) {
   if (st && !(g.ablate & 8)) st_i32<V>(g.C + off, v, g.nt);
   if (!kBlock) return;
-  const int qmin = (int)g.rq.qmin, qmax = (int)g.rq.qmax;
-  if (g.ch_is_row) {
+  const int32_t qmin = (int32_t)g.rq.qmin, qmax = (int32_t)g.rq.qmax, zpo = g.rq.zp_out;
+  const int mode = g.rq.mode;
 #pragma unroll
-    for (int q = 0; q < V; ++q) v[q] = (int32_t)((uint32_t)v[q] + (uint32_t)r.bias);
-    if (st && !(g.ablate & 16)) st_i32<V>(g.bias_out + off, v, g.nt);
-    const int mode = g.rq.mode;
-    if (mode == TK_RQ_AXIS_UPWARD || mode == TK_RQ_TENSOR_UPWARD) {
-      if (r.s <= -2) {
-        // right shift >= 2: the rounding constant 2^(30+rs) has a zero low word, so
-        // (x·m + 2^(30+rs)) >> (31+rs) only needs the high word of x·m (v_mul_hi_i32)
-        const int sh2 = -r.s - 1;
-        const uint32_t rnd = 1u << (sh2 - 1);
+  for (int q = 0; q < V; ++q) v[q] = (int32_t)((uint32_t)v[q] + (uint32_t)(g.ch_is_row ? r.bias : cc[q].bias));
+  if (st && !(g.ablate & 16)) st_i32<V>(g.bias_out + off, v, g.nt);
+  if (!g.ch_is_row) {
 #pragma unroll
-        for (int q = 0; q < V; ++q)
-          v[q] = (int32_t)((uint32_t)__mulhi((int32_t)((uint32_t)v[q] - (uint32_t)r.zp), r.m) + rnd) >> sh2;
-      } else {
+    for (int q = 0; q < V; ++q) v[q] = block_rq<false>((uint32_t)v[q], (uint32_t)cc[q].zp, cc[q].m, cc[q].s, mode, zpo, qmin, qmax);
+  } else if (block_rq_fast_ok(mode, r.s)) {
 #pragma unroll
-        for (int q = 0; q < V; ++q) v[q] = qms_upward((int32_t)((uint32_t)v[q] - (uint32_t)r.zp), r.m, r.s);
-      }
-    } else if (mode == TK_RQ_TENSOR_POW2) {
-#pragma unroll
-      for (int q = 0; q < V; ++q) v[q] = qms_pow2((int32_t)((uint32_t)v[q] - (uint32_t)r.zp), r.s);
-    } else if (mode == TK_RQ_IDENTITY) {
-#pragma unroll
-      for (int q = 0; q < V; ++q) v[q] = (int32_t)((uint32_t)v[q] - (uint32_t)r.zp);
-    } else {
-#pragma unroll
-      for (int q = 0; q < V; ++q) v[q] = qms_tonearest((int32_t)((uint32_t)v[q] - (uint32_t)r.zp), r.m, r.s);
-    }
-#pragma unroll
-    for (int q = 0; q < V; ++q) v[q] = min(max((int32_t)((uint32_t)g.rq.zp_out + (uint32_t)v[q]), qmin), qmax);
+    for (int q = 0; q < V; ++q) v[q] = block_rq<true>((uint32_t)v[q], (uint32_t)r.zp, r.m, r.s, mode, zpo, qmin, qmax);
   } else {
-    // channel = column (dense blocks): per-column constants from registers
 #pragma unroll
-    for (int q = 0; q < V; ++q) v[q] = (int32_t)((uint32_t)v[q] + (uint32_t)cc[q].bias);
-    if (st && !(g.ablate & 16)) st_i32<V>(g.bias_out + off, v, g.nt);
-    const int mode = g.rq.mode;
-#pragma unroll
-    for (int q = 0; q < V; ++q) {
-      const int32_t t = rq_core((int32_t)((uint32_t)v[q] - (uint32_t)cc[q].zp), mode, cc[q].m, cc[q].s);
-      v[q] = min(max((int32_t)((uint32_t)g.rq.zp_out + (uint32_t)t), qmin), qmax);
-    }
+    for (int q = 0; q < V; ++q) v[q] = block_rq<false>((uint32_t)v[q], (uint32_t)r.zp, r.m, r.s, mode, zpo, qmin, qmax);
   }
   if (st && !(g.ablate & 32)) st_i8<V>(g.rq_out + off, v, g.nt);
   if (g.has_add) {
-    // qnn.add (src/relay/qnn/op/add.cc:40-96): RQ(block) + RQ(residual) - zp_out, clip to the dtype
-    const int tlo = (int)g.rq.qmin, thi = (int)g.rq.qmax;
 #pragma unroll
-    for (int q = 0; q < V; ++q) {
-      const uint32_t rb = (resid >> (8 * q)) & 0xFFu;
-      const int32_t o = (int32_t)((uint32_t)lut[v[q] & 0xFF] + (uint32_t)lut[256 + rb] - (uint32_t)g.add_zp);
-      v[q] = min(max(o, tlo), thi);
-    }
+    for (int q = 0; q < V; ++q) v[q] = block_join(v[q], (resid >> (8 * q)) & 0xFFu, lut, g.add_zp, qmin, qmax);
     if (st) st_i8<V>(g.add_out + off, v, g.nt);
   }
   if (g.has_clip) {
 #pragma unroll
-    for (int q = 0; q < V; ++q) v[q] = min(max(v[q], g.clip_lo), g.clip_hi);
+    for (int q = 0; q < V; ++q) v[q] = block_clip(v[q], g.clip_lo, g.clip_hi);
     if (st && !(g.ablate & 64)) st_i8<V>(g.clip_out + off, v, g.nt);
   }
 }
@@ -230,7 +178,7 @@ gemm_i8_kernel(GemmArgs g) {
   constexpr int kStage = (kIm2col ? kRing : 2) * kStageBytes;
   constexpr int kEpi = BM * kStr * 4 + BM * (int)sizeof(EpiRow) + (kBlock ? 512 * 4 + 16 : 0);  // + flat sink slot
   __shared__ __attribute__((aligned(16))) int8_t smem[kStage > kEpi ? kStage : kEpi];
-  __shared__ int s_fast;  // tile-uniform: every row's requantize takes the mul_hi form (shift <= -2)
+  __shared__ int s_fast;  // tile-uniform: every row's shift admits the mul_hi form (block_rq_fast_shift)
   int8_t* As = smem;
   int8_t* Bs = smem + 2 * BM * kBK;
 
@@ -688,14 +636,11 @@ gemm_i8_kernel(GemmArgs g) {
       if (!g.rq.zps) r.zp = g.rq.zp_in;
     }
     r.fold = (uint32_t)g.k_eff * r.za * (uint32_t)g.zB - (uint32_t)g.zB * r.ra;
-    if (kBlock && g.ch_is_row && r.s > -2) s_fast = 0;
+    if (kBlock && g.ch_is_row && !block_rq_fast_shift(r.s)) s_fast = 0;
     rowc[tid] = r;
   }
   if (kBlock && g.has_add) {
-    // RequantizeOrUpcast of every 8-bit value of both qnn.add operands (op_common.h:186-200)
-    const int32_t x = g.rq.qmin == 0 ? tid : (int32_t)(int8_t)(uint8_t)tid;
-    lut[tid] = g.add_up_b ? x : rq_tensor(x, g.add_pb);
-    lut[256 + tid] = g.add_up_r ? x : rq_tensor(x, g.add_pr);
+    block_join_lut(tid, lut, g.rq.qmin == 0, g.add_up_b, g.add_up_r, g.add_pb, g.add_pr);
   }
 #pragma unroll
   for (int i = 0; i < MT; ++i) {
@@ -720,7 +665,6 @@ gemm_i8_kernel(GemmArgs g) {
       // stores of the int32 records and b32 stores of the 8-bit ones, contiguous across lanes
       // (whole 128-byte lines), each element gathered from its (row, column) slot of the tile.
       done = true;
-      const int hw = g.OH * g.OW;
       const int run = min(BM, g.M - m0) * hw;
       const int img0 = n0 / hw, nimg = g.N / hw;
       const uint32_t n4 = g.out_elems * 4u;
@@ -776,31 +720,20 @@ gemm_i8_kernel(GemmArgs g) {
           if (!TK_ABL(2)) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i, v), r_bias, o * 4u, 0, kAuxNT);
           int32_t q[4];
 #pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const int32_t t = (int32_t)(v[e] - (uint32_t)rr[e].zp);
-            int32_t y;
-            if constexpr (FAST) {
-              const int sh2 = -rr[e].s - 1;
-              y = (int32_t)((uint32_t)__mulhi(t, rr[e].m) + (1u << (sh2 - 1))) >> sh2;
-            } else {
-              y = rq_core(t, mode, rr[e].m, rr[e].s);
-            }
-            q[e] = clamp_i32((int32_t)((uint32_t)zpo + (uint32_t)y), qmin, qmax);
-          }
+          for (int e = 0; e < 4; ++e)
+            q[e] = block_rq<FAST>(v[e], (uint32_t)rr[e].zp, rr[e].m, rr[e].s, mode, zpo, qmin, qmax);
           if (!TK_ABL(2)) __builtin_amdgcn_raw_buffer_store_b32(pack4u(q[0], q[1], q[2], q[3]), r_rq, o, 0, kAuxNT);
           if (has_add) {
-            // qnn.add (src/relay/qnn/op/add.cc:40-96): RQ(block) + RQ(residual) - zp_out
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               const uint32_t rb = (resid_pre[k] >> (8 * e)) & 0xFFu;
-              q[e] = clamp_i32(TK_ABL(8192) ? q[e] + (int32_t)rb - add_zp : lut[q[e] & 0xFF] + lut[256 + rb] - add_zp,
-                               qmin, qmax);
+              q[e] = TK_ABL(8192) ? clamp_i32(q[e] + (int32_t)rb - add_zp, qmin, qmax) : block_join(q[e], rb, lut, add_zp, qmin, qmax);
             }
             if (!TK_ABL(16384 | 2)) __builtin_amdgcn_raw_buffer_store_b32(pack4u(q[0], q[1], q[2], q[3]), r_add, o, 0, kAuxNT);
           }
           if (has_clip) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) q[e] = clamp_i32(q[e], clip_lo, clip_hi);
+            for (int e = 0; e < 4; ++e) q[e] = block_clip(q[e], clip_lo, clip_hi);
             if (!TK_ABL(2)) __builtin_amdgcn_raw_buffer_store_b32(pack4u(q[0], q[1], q[2], q[3]), r_clip, o, 0, kAuxNT);
           }
           if constexpr (ROWU) {
@@ -884,31 +817,18 @@ gemm_i8_kernel(GemmArgs g) {
           for (int e = 0; e < 4; ++e) v[e] += (uint32_t)bias[e];
           if (!TK_ABL(2)) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i, v), r_bias, o * 4u, 0, kAuxNT);
           int32_t q[4];
-          if constexpr (FAST) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const int sh2 = -sh[e] - 1;
-              q[e] = clamp_i32(zpo + ((int32_t)((uint32_t)__mulhi((int32_t)(v[e] - zp[e]), m[e]) + (1u << (sh2 - 1))) >> sh2),
-                               qmin, qmax);
-            }
-          } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-              q[e] = clamp_i32((int32_t)((uint32_t)zpo + (uint32_t)rq_core((int32_t)(v[e] - zp[e]), mode, m[e], sh[e])),
-                               qmin, qmax);
-          }
+          for (int e = 0; e < 4; ++e) q[e] = block_rq<FAST>(v[e], zp[e], m[e], sh[e], mode, zpo, qmin, qmax);
           if (!TK_ABL(2)) __builtin_amdgcn_raw_buffer_store_b32(pack4u(q[0], q[1], q[2], q[3]), r_rq, o, 0, kAuxNT);
           if constexpr (ADD) {
-            // qnn.add (src/relay/qnn/op/add.cc:40-96): RQ(block) + RQ(residual) - zp_out
             const uint32_t res = resid_pre[k];
 #pragma unroll
-            for (int e = 0; e < 4; ++e)
-              q[e] = clamp_i32(lut[q[e] & 0xFF] + lut[256 + ((res >> (8 * e)) & 0xFFu)] - add_zp, qmin, qmax);
+            for (int e = 0; e < 4; ++e) q[e] = block_join(q[e], (res >> (8 * e)) & 0xFFu, lut, add_zp, qmin, qmax);
             if (!TK_ABL(2)) __builtin_amdgcn_raw_buffer_store_b32(pack4u(q[0], q[1], q[2], q[3]), r_add, o, 0, kAuxNT);
           }
           if constexpr (CLIP) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) q[e] = clamp_i32(q[e], clip_lo, clip_hi);
+            for (int e = 0; e < 4; ++e) q[e] = block_clip(q[e], clip_lo, clip_hi);
             if (!TK_ABL(2)) __builtin_amdgcn_raw_buffer_store_b32(pack4u(q[0], q[1], q[2], q[3]), r_clip, o, 0, kAuxNT);
           }
           if constexpr (XR) {
@@ -930,7 +850,7 @@ gemm_i8_kernel(GemmArgs g) {
           else lean(fast_c, F{}, F{}, xr_c);
         }
       };
-      const bool fastrq = s_fast && (mode == TK_RQ_AXIS_UPWARD || mode == TK_RQ_TENSOR_UPWARD);
+      const bool fastrq = s_fast && block_rq_fast_mode(mode);
       if (TK_ABL(65536)) {
       } else if (hw % 4 == 0 && hw >= 16 && !TK_ABL(32768)) {
         if (fastrq) lean_fast(std::true_type{}, std::false_type{});
@@ -948,7 +868,7 @@ gemm_i8_kernel(GemmArgs g) {
     } else if (g.fast_epi && simple_fold && s_fast && !(g.ablate & 0x7D)) {
       // ---- fast path (tile-uniform): 4 consecutive columns x rows (tid>>5) + 8k, every
       // record through a buffer descriptor (masked lanes get an out-of-range offset),
-      // requantize in the mul_hi form: ((x - zp)·m + 2^(sh2-1)) >> sh2 over the high word
+      // requantize in the mul_hi form (block_rq<true>)
       done = true;
       const int c4 = (tid % kLPR) * 4;
       const int col = n0 + c4;
@@ -964,6 +884,7 @@ gemm_i8_kernel(GemmArgs g) {
       // kernel arguments the row loop needs, held in registers: read through `g` after a
       // store, the compiler reloads them (s_load + lgkmcnt(0), which also drains the LDS reads)
       const int32_t add_zp = g.add_zp, clip_lo = g.clip_lo, clip_hi = g.clip_hi;
+      const int mode = g.rq.mode;
       const bool want_shadow = g.shadow_out != nullptr;
       uint32_t offs[kRows];
 #pragma unroll
@@ -989,12 +910,8 @@ gemm_i8_kernel(GemmArgs g) {
               __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i, v), r_conv, o * 4u, 0, AUX);
               v += (uint32_t)r.bias;
               __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i, v), r_bias, o * 4u, 0, AUX);
-              const int sh2 = -r.s - 1;
-              const uint32_t rnd = 1u << (sh2 - 1);
 #pragma unroll
-              for (int e = 0; e < 4; ++e)
-                qs[k][e] = clamp_i32(zpo + ((int32_t)((uint32_t)__mulhi((int32_t)(v[e] - (uint32_t)r.zp), r.m) + rnd) >> sh2),
-                                     qmin, qmax);
+              for (int e = 0; e < 4; ++e) qs[k][e] = block_rq<true>(v[e], (uint32_t)r.zp, r.m, r.s, mode, zpo, qmin, qmax);
               __builtin_amdgcn_raw_buffer_store_b32(pack4u(qs[k][0], qs[k][1], qs[k][2], qs[k][3]), r_rq, o, 0, AUX);
             }
 #pragma unroll
@@ -1003,15 +920,12 @@ gemm_i8_kernel(GemmArgs g) {
               const uint32_t o = offs[k];
               int32_t q[4];
 #pragma unroll
-              for (int e = 0; e < 4; ++e) {
-                // qnn.add (src/relay/qnn/op/add.cc:40-96): RQ(block) + RQ(residual) - zp_out
-                const uint32_t rb = (resid_pre[k] >> (8 * e)) & 0xFFu;
-                q[e] = clamp_i32(lut[qs[k][e] & 0xFF] + lut[256 + rb] - add_zp, qmin, qmax);
-              }
+              for (int e = 0; e < 4; ++e)
+                q[e] = block_join(qs[k][e], (resid_pre[k] >> (8 * e)) & 0xFFu, lut, add_zp, qmin, qmax);
               __builtin_amdgcn_raw_buffer_store_b32(pack4u(q[0], q[1], q[2], q[3]), r_add, o, 0, AUX);
               if constexpr (CLIP) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) q[e] = clamp_i32(q[e], clip_lo, clip_hi);
+                for (int e = 0; e < 4; ++e) q[e] = block_clip(q[e], clip_lo, clip_hi);
                 __builtin_amdgcn_raw_buffer_store_b32(pack4u(q[0], q[1], q[2], q[3]), r_clip, o, 0, AUX);
               }
               if (want_shadow) *reinterpret_cast<v4i*>(tileI + lr * kStr + c4) = v4i{q[0], q[1], q[2], q[3]};
@@ -1041,27 +955,21 @@ gemm_i8_kernel(GemmArgs g) {
           if (!TK_ABL(2)) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i, v), r_conv, o * 4u, 0, AUX);
           v += (uint32_t)r.bias;
           if (!TK_ABL(2)) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i, v), r_bias, o * 4u, 0, AUX);
-          const int sh2 = -r.s - 1;
-          const uint32_t rnd = 1u << (sh2 - 1);
           int32_t q[4];
 #pragma unroll
-          for (int e = 0; e < 4; ++e)
-            q[e] = clamp_i32(zpo + ((int32_t)((uint32_t)__mulhi((int32_t)(v[e] - (uint32_t)r.zp), r.m) + rnd) >> sh2),
-                             qmin, qmax);
+          for (int e = 0; e < 4; ++e) q[e] = block_rq<true>(v[e], (uint32_t)r.zp, r.m, r.s, mode, zpo, qmin, qmax);
           if (!TK_ABL(2)) __builtin_amdgcn_raw_buffer_store_b32(pack4u(q[0], q[1], q[2], q[3]), r_rq, o, 0, AUX);
           if constexpr (ADD) {
-            // qnn.add (src/relay/qnn/op/add.cc:40-96): RQ(block) + RQ(residual) - zp_out
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               const uint32_t rb = (resid_pre[k] >> (8 * e)) & 0xFFu;
-              q[e] = clamp_i32(TK_ABL(8192) ? q[e] + (int32_t)rb - add_zp : lut[q[e] & 0xFF] + lut[256 + rb] - add_zp,
-                               qmin, qmax);
+              q[e] = TK_ABL(8192) ? clamp_i32(q[e] + (int32_t)rb - add_zp, qmin, qmax) : block_join(q[e], rb, lut, add_zp, qmin, qmax);
             }
             if (!TK_ABL(16384 | 2)) __builtin_amdgcn_raw_buffer_store_b32(pack4u(q[0], q[1], q[2], q[3]), r_add, o, 0, AUX);
           }
           if constexpr (CLIP) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) q[e] = clamp_i32(q[e], clip_lo, clip_hi);
+            for (int e = 0; e < 4; ++e) q[e] = block_clip(q[e], clip_lo, clip_hi);
             if (!TK_ABL(2)) __builtin_amdgcn_raw_buffer_store_b32(pack4u(q[0], q[1], q[2], q[3]), r_clip, o, 0, AUX);
           }
           if (want_shadow) *reinterpret_cast<v4i*>(slot) = v4i{q[0], q[1], q[2], q[3]};
@@ -1114,9 +1022,9 @@ gemm_i8_kernel(GemmArgs g) {
       cbase = col;
       rstride = g.ldc;
     }
-    EpiRow cc[4] = {};
+    BlockConsts cc[4] = {};
     if (kBlock && !g.ch_is_row)
-      for (int q = 0; q < 4; ++q) cc[q] = col_consts(g, col + q);
+      for (int q = 0; q < 4; ++q) cc[q] = block_consts(g.bias, g.rq, min(col + q, g.N - 1));
 #pragma unroll
     for (int k = 0; k < kRows; ++k) {
       const int lr = tid / kLPR + kRPI * k;
@@ -1137,8 +1045,8 @@ gemm_i8_kernel(GemmArgs g) {
     const int lc = tid & (BN - 1);
     const int col = n0 + lc;
     const bool colok = col < g.N;
-    EpiRow cc1{};
-    if (kBlock && !g.ch_is_row) cc1 = col_consts(g, col);
+    BlockConsts cc1{};
+    if (kBlock && !g.ch_is_row) cc1 = block_consts(g.bias, g.rq, min(col, g.N - 1));
     int64_t cbase = col, rstride = g.ldc;
     if (g.out_nchw) {
       const int img = col / hw;
@@ -1440,16 +1348,16 @@ __global__ __launch_bounds__(256) void dw3x3_kernel(const Tx* __restrict__ x, co
 #pragma unroll
     for (int e = 0; e < V; ++e) v[e] = acc[e];
     st_i32<V>(g.C + off, v, false);
-    const int32_t bias = g.bias[ch];
+    const BlockConsts k = block_consts(g.bias, g.rq, ch);
 #pragma unroll
-    for (int e = 0; e < V; ++e) v[e] = (int32_t)((uint32_t)v[e] + (uint32_t)bias);
+    for (int e = 0; e < V; ++e) v[e] = (int32_t)((uint32_t)v[e] + (uint32_t)k.bias);
     st_i32<V>(g.bias_out + off, v, false);
 #pragma unroll
-    for (int e = 0; e < V; ++e) v[e] = min(max(rq_apply(v[e], ch, g.rq), qmin), qmax);
+    for (int e = 0; e < V; ++e) v[e] = block_rq<false>((uint32_t)v[e], (uint32_t)k.zp, k.m, k.s, g.rq.mode, g.rq.zp_out, qmin, qmax);
     st_i8<V>(g.rq_out + off, v, false);
     if (g.has_clip) {
 #pragma unroll
-      for (int e = 0; e < V; ++e) v[e] = min(max(v[e], g.clip_lo), g.clip_hi);
+      for (int e = 0; e < V; ++e) v[e] = block_clip(v[e], g.clip_lo, g.clip_hi);
       st_i8<V>(g.clip_out + off, v, false);
     }
 #pragma unroll
@@ -1923,8 +1831,7 @@ static int conv2d_run(const tk_tensor* data, const void* shadow, const tk_tensor
     // planes) run up to 1.9x slower than plain ones, which the L2 merges before write-back
     const int hwp = g.OH * g.OW;
     const int epi = hwp % 32 == 0 || hwp <= 64 ? 1 : 2;
-    ga.fast_epi = blk && elems * 4 < 0xFFFFFFC0ull && hwp % 4 == 0 &&
-                  (mode == TK_RQ_AXIS_UPWARD || mode == TK_RQ_TENSOR_UPWARD) ? env_int("TK_FASTEPI", epi) : 0;
+    ga.fast_epi = blk && elems * 4 < 0xFFFFFFC0ull && hwp % 4 == 0 && block_rq_fast_mode(mode) ? env_int("TK_FASTEPI", epi) : 0;
   }
   ga.out_nchw = 1;
   {
@@ -2109,8 +2016,7 @@ int conv2d_block_algos_impl(const tk_tensor* data, const tk_tensor* weight, cons
     // the same gates (incl. the TK_FASTEPI / TK_UNITAP overrides) as conv2d_run, so that every
     // algo listed here runs there
     const int epi = hw % 32 == 0 || hw <= 64 ? 1 : 2;
-    pa.fast_epi = P * g.O * 4 < 0xFFFFFFC0ll && hw % 4 == 0 && (mode == TK_RQ_AXIS_UPWARD || mode == TK_RQ_TENSOR_UPWARD)
-                      ? env_int("TK_FASTEPI", epi) : 0;
+    pa.fast_epi = P * g.O * 4 < 0xFFFFFFC0ll && hw % 4 == 0 && block_rq_fast_mode(mode) ? env_int("TK_FASTEPI", epi) : 0;
     pa.unitap = taps <= 64 && (g.cin_pad % kBK == 0 || taps == 1) && env_int("TK_UNITAP", 1);
     pa.ch_is_row = 1;
     pa.out_nchw = 1;

@@ -3,8 +3,8 @@
 // qnn.add canonicalises to  o = RQ(a) + RQ(b) - zp_c ; clip+cast to the input dtype
 // (src/relay/qnn/op/add.cc:40-96, op_common.h:169-207), where RQ is a per-tensor
 // requantize to int32 or a plain upcast.  With 8-bit operands RQ has 256 possible
-// inputs, so each workgroup tabulates RQ for both operands in LDS once (computed with
-// the same rq_apply the requantize kernel uses, hence bit-exact by construction) and
+// inputs, so each workgroup tabulates RQ for both operands in LDS once (block_join_lut: computed
+// with the same rq_apply the requantize kernel uses, hence bit-exact by construction) and
 // the element loop is two table lookups, an add and two clamps: the kernel is a pure
 // HBM stream of 2 bytes in, 2 bytes out (+ the shadow) per element.
 //
@@ -16,6 +16,7 @@
 // (tk_conv2d_make_shadow layout); channels >= C are written as 0.
 #include <algorithm>
 
+#include "tk_block_tail.h"
 #include "tk_ops.h"
 
 namespace tk {
@@ -47,15 +48,10 @@ __device__ __forceinline__ uint32_t gather_byte(uint32_t w0, uint32_t w1, uint32
 template <int kV>
 __global__ __launch_bounds__(kThreads) void add_block_kernel(AddBlockArgs g) {
   constexpr int kW = kV >= 4 ? kV / 4 : 1;  // dwords per channel row of the unit
-  __shared__ int32_t lut_a[256];
-  __shared__ int32_t lut_b[256];
+  __shared__ int32_t lut[512];
+  const int32_t *lut_a = lut, *lut_b = lut + 256;
   const int tid = threadIdx.x;
-  {
-    // RequantizeOrUpcast of every representable 8-bit value (op_common.h:186-200)
-    int32_t x = g.is_u8 ? tid : (int32_t)(int8_t)(uint8_t)tid;
-    lut_a[tid] = g.up_a ? x : rq_apply(x, 0, g.pa);
-    lut_b[tid] = g.up_b ? x : rq_apply(x, 0, g.pb);
-  }
+  block_join_lut(tid, lut, g.is_u8, g.up_a, g.up_b, g.pa, g.pb);
   __syncthreads();
 
   const int tmin = g.is_u8 ? 0 : -128, tmax = g.is_u8 ? 255 : 127;
@@ -141,15 +137,11 @@ __global__ __launch_bounds__(kThreads) void add_block_kernel(AddBlockArgs g) {
 constexpr int kPlaneLds = 16384;
 
 __global__ __launch_bounds__(kThreads) void add_block_plane_kernel(AddBlockArgs g, int K) {
-  __shared__ int32_t lut_a[256];
-  __shared__ int32_t lut_b[256];
+  __shared__ int32_t lut[512];
   __shared__ __attribute__((aligned(16))) uint8_t tile[kPlaneLds];
+  const int32_t *lut_a = lut, *lut_b = lut + 256;
   const int tid = threadIdx.x;
-  {
-    int32_t x = g.is_u8 ? tid : (int32_t)(int8_t)(uint8_t)tid;
-    lut_a[tid] = g.up_a ? x : rq_apply(x, 0, g.pa);
-    lut_b[tid] = g.up_b ? x : rq_apply(x, 0, g.pb);
-  }
+  block_join_lut(tid, lut, g.is_u8, g.up_a, g.up_b, g.pa, g.pb);
   __syncthreads();
   const int tmin = g.is_u8 ? 0 : -128, tmax = g.is_u8 ? 255 : 127;
   const int blk = 16 * g.HW;

@@ -134,6 +134,8 @@ GEOMETRIES = [
     Geometry("dw_flat", "depthwise flat groups", (2, 64, 7, 7), 64, k=3, pad=1, groups=64),
     Geometry("dw_u8_zwvec", "depthwise, uint8 data, per-channel kernel zero points", (2, 32, 14, 14), 32, k=3, pad=1,
              groups=32, dtype="uint8", zw_vec=True),
+    Geometry("dw_band_pad3", "depthwise band kernel (padding above 2: the tile kernel declines; 32x32 outputs)",
+             (1, 16, 28, 28), 16, k=3, pad=3, groups=16),
     Geometry("direct_5x5", "direct kernel (tiny Cin, O < 16)", (1, 1, 12, 12), 6, k=5, pad=2),
     Geometry("dense_5x84x10", "tk_qnn_dense_block, one ragged tile", (5, 84), 10, dense=True),
     Geometry("dense_130x70x129", "tk_qnn_dense_block, four tiles, uint8 data, kernel zero point 2", (130, 70), 129,
