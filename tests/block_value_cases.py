@@ -51,7 +51,7 @@ conditions also hold in the records of 50 and 864 elements, where few channels a
 import functools
 import zlib
 from dataclasses import dataclass, field
-from typing import Optional, Tuple
+from typing import Optional, Tuple, Union
 
 import numpy as np
 
@@ -74,15 +74,20 @@ VARIANTS = [
 ]
 
 
+def _tup(v, n):
+    """An attribute given as one value for every axis or side, or as its n values."""
+    return (v,) * n if isinstance(v, int) else tuple(v)
+
+
 @dataclass(frozen=True)
 class Geometry:
     name: str
     meant: str                      # the kernel family this shape is here for
     x_shape: Tuple[int, ...]        # NCHW, or [M, K] of a dense block
     o: int
-    k: int = 1
-    stride: int = 1
-    pad: int = 0
+    k: Union[int, Tuple[int, int]] = 1                  # one value for both axes, or (KH, KW)
+    stride: Union[int, Tuple[int, int]] = 1             # ... or (sh, sw)
+    pad: Union[int, Tuple[int, int, int, int]] = 0      # one value for all sides, or (pt, pl, pb, pr)
     groups: int = 1
     dtype: str = "int8"             # data, residual and output dtype
     zw: int = 0
@@ -90,6 +95,8 @@ class Geometry:
     residual: bool = False
     block_is_rhs: bool = False
     dense: bool = False             # tk_qnn_dense_block instead of tk_qnn_conv2d_block
+    dilation: Union[int, Tuple[int, int]] = 1           # one value for both axes, or (dh, dw)
+    w_dtype: str = "int8"           # weight dtype
 
     @property
     def za(self):
@@ -108,11 +115,12 @@ class Geometry:
     def w_shape(self):
         if self.dense:
             return self.o, self.x_shape[1]
-        return self.o, self.x_shape[1] // self.groups, self.k, self.k
+        return (self.o, self.x_shape[1] // self.groups) + _tup(self.k, 2)
 
     @property
     def conv_kw(self):
-        return dict(strides=(self.stride,) * 2, padding=(self.pad,) * 4, groups=self.groups)
+        return dict(strides=_tup(self.stride, 2), padding=_tup(self.pad, 4), dilation=_tup(self.dilation, 2),
+                    groups=self.groups)
 
 
 GEOMETRIES = [
@@ -202,7 +210,7 @@ def operands(name: str, small: bool):
         w = rng.integers(-1, 2, size=g.w_shape).astype(np.int8)
     else:
         x = _uniform(rng, g.x_shape, g.dtype)
-        w = _uniform(rng, g.w_shape, "int8")
+        w = _uniform(rng, g.w_shape, g.w_dtype)
     zv = rng.integers(-6, 7, size=g.o).astype(np.int32) if g.zw_vec else None
     zw = zv if zv is not None else g.zw
     conv = ref.qnn_dense(x, w, g.za, zw) if g.dense else ref.qnn_conv2d(x, w, g.za, zw, **g.conv_kw)
@@ -267,8 +275,13 @@ def _draw(g: Geometry, regime: str, mode: str, conv):
 
 def build(name: str, regime: str, mode: str) -> Case:
     """The case of one geometry x regime x mode, with every expected record from the oracle."""
-    g = GEOMETRY[name]
-    x, w, zv, conv = operands(name, regime == "small")
+    return chain(GEOMETRY[name], regime, mode, *operands(name, regime == "small"))
+
+
+def chain(g: Geometry, regime: str, mode: str, x, w, zv, conv) -> Case:
+    """The case of a geometry's operands and conv record under regime x mode: the draws of _draw and
+    the oracle's records after the conv."""
+    name = g.name
     bias, s_in, rq_zp = _draw(g, regime, mode, conv)
     rounding = "TONEAREST" if mode.endswith("TONEAREST") else "UPWARD"
     badd = ref.bias_add(conv, bias, 1)
