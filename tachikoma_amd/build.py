@@ -30,9 +30,9 @@ BUILD = os.path.join(HERE, "_build")
 LIB = os.path.join(HERE, "libtachikoma.so")
 ARCH = "gfx950"
 
-SOURCES = ["tk_host.cc", "tk_calibrate.cc", "tk_format.cc", "tk_wire.cc", "tk_capture_plan.cc", "tk_capture.cc", "tk_runtime.cc", "tk_elementwise.hip", "tk_trace.hip", "tk_shadow.hip", "tk_chain.hip", "tk_stats.hip", "tk_fstats.hip", "tk_kl.hip",
-           "tk_gemm.hip", "tk_residual.hip", "tk_realize.hip", "tk_conv_img.hip", "tk_conv_pf.hip", "tk_qnn_ops.hip", "tk_dense.hip", "tk_dw.hip"]
-HEADERS = ["tk_common.h", "tk_tensor.h", "tk_node.h", "tk_ops.h", "tk_module.h", "tk_capture_plan.h", "tk_conv.h", "tk_block_tail.h", "tk_wire.h",
+SOURCES = ["tk_host.cc", "tk_calibrate.cc", "tk_format.cc", "tk_wire.cc", "tk_capture_plan.cc", "tk_capture.cc", "tk_conv_plan.cc", "tk_runtime.cc", "tk_elementwise.hip", "tk_trace.hip", "tk_shadow.hip", "tk_chain.hip", "tk_stats.hip", "tk_fstats.hip", "tk_kl.hip",
+           "tk_gemm.hip", "tk_conv.cc", "tk_conv_prep.hip", "tk_conv_direct.hip", "tk_residual.hip", "tk_realize.hip", "tk_conv_img.hip", "tk_conv_pf.hip", "tk_qnn_ops.hip", "tk_dense.hip", "tk_dw.hip"]
+HEADERS = ["tk_common.h", "tk_tensor.h", "tk_node.h", "tk_ops.h", "tk_module.h", "tk_capture_plan.h", "tk_conv.h", "tk_conv_plan.h", "tk_block_tail.h", "tk_wire.h",
            "tk_chain.h", "tk_fstats.h", "tk_kl.h"]
 BASE_FLAGS = ["-std=c++20", "-O3", "-fPIC", "-fvisibility=hidden", f"--offload-arch={ARCH}", "-Wall",
               "-Wno-unused-function"]
@@ -172,7 +172,7 @@ def _build_into(obj_dir: str, lib: str, defines, tag: str, force: bool, verbose:
 
 def build_ablation(verbose: bool = True) -> str:
     """Profiling variant with the kernel-selection and main-loop ablation switches read from
-    the environment (TK_ABLATE, TK_XCD, TK_RING, ...; see tune_env in csrc/tk_gemm.hip):
+    the environment (TK_ABLATE, TK_XCD, TK_RING, ...; see tune_env in csrc/tk_conv_plan.h):
     tachikoma_amd/_ab/libtachikoma_ablate.so, loaded by the tools through TK_LIB_PATH.  The
     product library has them compiled out."""
     return _build_into(os.path.join(BUILD, "ablate"), os.path.join(HERE, "_ab", "libtachikoma_ablate.so"),

@@ -1,24 +1,21 @@
-// Definitions shared by the conv / dense block kernels (tk_gemm.hip: im2col, patch, direct and
-// band kernels and the host dispatch; tk_conv_img.hip: image-tile kernel; tk_conv_pf.hip:
-// persistent im2col kernel; tk_dw.hip: depthwise tile kernel; tk_dense.hip: small-batch dense
-// tiles): kernel arguments, the fused block epilogue's per-row constants, device helpers and the
-// host-side conv geometry.  The block tail's arithmetic is tk_block_tail.h.
+// Definitions shared by the conv / dense block kernels (tk_gemm.hip: gemm_i8_kernel, its variant
+// table and the dense path; tk_conv.cc: the conv host dispatch; tk_conv_prep.hip: operand
+// preparation; tk_conv_direct.hip: direct and band kernels; tk_conv_img.hip: image-tile kernel;
+// tk_conv_pf.hip: persistent im2col kernel; tk_dw.hip: depthwise tile kernel; tk_dense.hip:
+// small-batch dense tiles): kernel arguments, the fused block epilogue's per-row constants, device
+// helpers and what the files call of each other.  The host-side plan (geometry, traits, tile plan,
+// layouts) is tk_conv_plan.h; the block tail's arithmetic is tk_block_tail.h.
 #pragma once
-
-#include <cstdlib>
 
 #include "tk_block_tail.h"
 #include "tk_common.h"
+#include "tk_conv_plan.h"
 
 namespace tk {
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-
-constexpr int kBK = 64;          // bytes of K per stage
-constexpr int kGemmThreads = 256;
-
 
 struct GemmArgs {
   const int8_t* A;     // [rowsA_pad][lda]
@@ -186,11 +183,6 @@ __device__ __forceinline__ uint32_t fdiv40(uint32_t x, uint64_t mg) { return (ui
 __device__ __forceinline__ uint32_t fdiv32(uint32_t x, uint32_t m) { return __umulhi(x, m); }
 
 
-struct ConvGeom {
-  int N, C, H, W, O, KH, KW, OH, OW, cin_pad, k_pad, k_eff, rows_pad;
-};
-
-
 // Block outputs (NULL `b` = plain conv/dense writing only the int32 contraction).
 struct BlockIO {
   const tk_tensor* bias;
@@ -201,17 +193,45 @@ struct BlockIO {
 };
 
 
-#ifdef TK_ABLATION_BUILD
-static const char* tune_env(const char* name) { return getenv(name); }
-#else
-static const char* tune_env(const char*) { return nullptr; }
-#endif
-
-
-static int env_int(const char* name, int dflt) {
-  const char* e = tune_env(name);
-  return e ? atoi(e) : dflt;
+// ---------------------------------------------------------------- record stores (nontemporal: see store_nt in tk_common.h)
+template <int V>
+__device__ __forceinline__ void st_i32(int32_t* dst, const int32_t* v, bool nt) {
+  if constexpr (V == 4) {
+    if (nt) __builtin_nontemporal_store(v4i{v[0], v[1], v[2], v[3]}, reinterpret_cast<v4i*>(dst));
+    else *reinterpret_cast<v4i*>(dst) = v4i{v[0], v[1], v[2], v[3]};
+  } else {
+    *dst = v[0];  // partial lines: let L2 merge them
+  }
 }
+
+template <int V>
+__device__ __forceinline__ void st_i8(uint8_t* dst, const int32_t* v, bool nt) {
+  if constexpr (V == 4) {
+    const uint32_t w = pack4u(v[0], v[1], v[2], v[3]);
+    if (nt) __builtin_nontemporal_store(w, reinterpret_cast<uint32_t*>(dst));
+    else *reinterpret_cast<uint32_t*>(dst) = w;
+  } else {
+    *dst = (uint8_t)v[0];
+  }
+}
+
+// ---------------------------------------------------------------- gemm_i8_kernel, its arguments
+// (tk_gemm.hip) launches the instantiation a plan names; a key with no kernel is an error.
+int gemm_launch(const GemmVariant& v, dim3 grid, unsigned lds_pad, const GemmArgs& ga, hipStream_t s);
+// (tk_conv.cc) validates a fused block and fills the epilogue part of GemmArgs
+int setup_block(GemmArgs& ga, const BlockIO* b, const tk_tensor* conv_out, int channels, int ch_axis);
+// (tk_conv_prep.hip) the per-pixel patch sums of a conv whose kernel zero point is not 0 (ga: the
+// im2col geometry); the padded rows of a dense operand [rows][K] with their sums
+int conv_patch_sums(const void* shadow, int32_t* out, const GemmArgs& ga, int cin, hipStream_t s);
+int dense_pad_rows(const tk_tensor* x, int8_t* padded, int32_t* sums, int rows_pad, int k_pad, hipStream_t s);
+
+// ---------------------------------------------------------------- grouped / depthwise / tiny convs
+// (tk_dw.hip) the depthwise 3x3 tile kernel (returns 1 and sets *rc when its plan applies)
+int dw_block_try(const tk_tensor* data, const tk_tensor* weight, const ConvGeom& g, const tk_conv2d_attrs* a,
+                 const GemmArgs& ga, hipStream_t s, int* rc);
+// (tk_conv_direct.hip) the depthwise band kernel where it applies, else the direct kernel
+int conv_direct_run(const tk_tensor* data, const tk_tensor* weight, const ConvGeom& g, const tk_conv2d_attrs* a,
+                    const GemmArgs& ga, bool block, hipStream_t s);
 
 // ---------------------------------------------------------------- image-tile conv blocks
 // (tk_conv_img.hip) whole-image tiles with the input patch + halo staged in LDS and the weights
@@ -227,27 +247,31 @@ int conv_img_pack(const tk_tensor* weight, int8_t* dst, int rows_pad, int cin_pa
 // 5: the small-batch dense tile kernel (tk_dense.hip) for dense blocks run as 1x1 conv blocks.
 constexpr int kAlgoIm2col = 1, kAlgoImg = 2, kAlgoPf2 = 3, kAlgoPf3 = 4, kAlgoDense = 5, kAlgoImg0 = 16;
 // Runs the conv block on the image-tile kernel when its plan applies (returns 1 and sets *rc;
-// algo 0: the cheapest plan by the planner's estimate), else returns 0 (im2col path).
+// algo 0: the cheapest plan by the planner's estimate), else returns 0 (im2col path).  The plans
+// come from the traits, the launch takes `ga`.
 // `chunked`: the chunked weight image (NULL for 1x1 convs, whose packed weight has that layout).
-int conv_img_try(const ConvGeom& g, const tk_conv2d_attrs* a, const GemmArgs& ga, const int8_t* chunked, void* scratch,
-                 int algo, hipStream_t s, int* rc);
+int conv_img_try(const ConvGeom& g, const tk_conv2d_attrs* a, const ConvTraits& t, const GemmArgs& ga,
+                 const int8_t* chunked, void* scratch, int algo, hipStream_t s, int* rc);
 // scratch a 3x3 block's split-K image-tile plans need (their partial records), 0 if none apply
 int64_t conv_img_split_scratch_bytes(const ConvGeom& g);
 // The image-tile plans as algo values (16 + i), cheapest estimate first; returns how many exist.
-int conv_img_algos(const ConvGeom& g, const tk_conv2d_attrs* a, const GemmArgs& ga, bool have_chunked,
+int conv_img_algos(const ConvGeom& g, const tk_conv2d_attrs* a, const ConvTraits& t, bool have_chunked,
                    int32_t* algos, int max_algos);
+// One plan's description (tk_conv2d_block_algo_info); TK_ERR_INVALID_ARG if `algo` is not listed.
+int conv_img_describe(const ConvGeom& g, const tk_conv2d_attrs* a, const ConvTraits& t, bool have_chunked, int algo,
+                      char* buf, int len);
 
 // ---------------------------------------------------------------- persistent im2col conv blocks
-// (tk_conv_pf.hip) whether the launch arguments (conv2d_run's, before the tile grid) suit the
-// persistent kernel, and its launch (ring: 2 or 3 slots).
-bool conv_pf_applies(const ConvGeom& g, const GemmArgs& ga);
+// (tk_conv_pf.hip) whether a block suits the persistent kernel, and its launch with conv2d_run's
+// arguments before the tile grid (ring: 2 or 3 slots).
+bool conv_pf_applies(const ConvGeom& g, const ConvTraits& t);
 int conv_pf_run(const ConvGeom& g, GemmArgs ga, int ring, hipStream_t s);
 
 // ---------------------------------------------------------------- small-batch dense blocks
 // (tk_dense.hip) [B, K] x [U, K]^T on 32 x 32 tiles with K split over the four waves, one launch.
-bool conv_dense_applies(const ConvGeom& g, const GemmArgs& ga);
+bool conv_dense_applies(const ConvGeom& g, const ConvTraits& t);
 // scratch: conv_dense_scratch_bytes(g) bytes for a K-sliced run (NULL: one launch, no slices)
-int conv_dense_run(const ConvGeom& g, const GemmArgs& ga, void* scratch, hipStream_t s);
+int conv_dense_run(const ConvGeom& g, const ConvTraits& t, const GemmArgs& ga, void* scratch, hipStream_t s);
 int64_t conv_dense_scratch_bytes(const ConvGeom& g);
 
 }  // namespace tk

@@ -752,7 +752,7 @@ constexpr int kImgMaxSplit = 4;  // split-K partial records a 3x3 block may need
 // workgroups per CU, the epilogue in npass column passes); false if it does not fit.
 // mode: 0 the whole block, 1 / 2 the partial / epilogue pass of a split-K plan over ksplit splits
 // (mode 1 needs no epilogue staging, mode 2 no ring)
-bool img_candidate(const ConvGeom& g, const GemmArgs& ga, int kt, int st, int R, int ipt, int CC, bool two,
+bool img_candidate(const ConvGeom& g, const ConvTraits& t, int kt, int st, int R, int ipt, int CC, bool two,
                    int npass, ImgPlan* out, int mode = 0, int ksplit = 1) {
   const int taps = kt * kt;
   const int hw = g.OH * g.OW;
@@ -795,7 +795,7 @@ bool img_candidate(const ConvGeom& g, const GemmArgs& ga, int kt, int st, int R,
   x.ni = ((x.sslots + 63) / 64 + 3) / 4;
   if (x.ni > kImgNI) return false;
   x.stage_bytes = 4 * x.ni * 1024;
-  const int64_t pstep = (int64_t)(CC / 16) * ga.in_pix * 16;
+  const int64_t pstep = (int64_t)(CC / 16) * t.in_pix * 16;
   if (pstep >= (1ll << 31)) return false;
   x.pstep = (int32_t)pstep;
   x.npass = npass;
@@ -806,7 +806,7 @@ bool img_candidate(const ConvGeom& g, const GemmArgs& ga, int kt, int st, int R,
   // ring depth: every slot the LDS budget holds (up to 8, no more than the stages need), at least
   // 3 where there are more than 2 stages and one workgroup per CU.  The budget is the CU's 160 KB, or half of it for two
   // resident workgroups (one's epilogue stores then overlap the other's K loop).
-  const size_t res_bytes = ga.has_add && mode != 1 ? ((size_t)(npass > 1 ? cw : p) * R + 255) / 256 * 256 : 0;
+  const size_t res_bytes = t.has_add && mode != 1 ? ((size_t)(npass > 1 ? cw : p) * R + 255) / 256 * 256 : 0;
   const size_t extra = mode == 1 ? 0 : (size_t)R * sizeof(EpiRow) + 2048 + res_bytes;
   const size_t tile = mode == 1 ? 0 : (size_t)R * x.tstride * 4;
   const int cap = env_int("TK_IMG_NS", 8);
@@ -834,7 +834,7 @@ bool img_candidate(const ConvGeom& g, const GemmArgs& ga, int kt, int st, int R,
                     (int64_t)g.OW, (int64_t)x.runq})
     if (d < 2 || d >= 65536) return false;
   if ((int64_t)R * cw >= 65536 || p >= 65536 || x.ni * 256 >= 65536 || 9ll * g.cin_pad >= (1ll << 24) ||
-      ga.lda >= (1ll << 24))
+      g.k_pad >= (1ll << 24))  // (the 1x1 plans' weight pitch)
     return false;
   x.m_cw = magic32(cw);
   x.m_pl = magic32(x.pl);
@@ -859,7 +859,7 @@ bool img_candidate(const ConvGeom& g, const GemmArgs& ga, int kt, int st, int R,
   const double bytes = R * K + (double)x.pl * g.cin_pad / (mode == 1 ? ksplit : 1);
   // (mode 2: reading the ksplit partial tiles instead of the K loop; mode 1: storing one)
   const double main_ns = mode == 2 ? (double)ksplit * R * p * 4 / 55.0 : std::max(bytes / 55.0, ct_need * K / 2.1);
-  const double epi_ns = mode == 1 ? (double)R * p * 4 / 22.0 : (double)R * p * (ga.has_add ? 12.0 : 10.0) / 22.0;
+  const double epi_ns = mode == 1 ? (double)R * p * 4 / 22.0 : (double)R * p * (t.has_add ? 12.0 : 10.0) / 22.0;
   const double per_cu = std::ceil(x.wgs / 256.0);
   const double lat = 2000.0;
   out->cost = two && per_cu >= 2 ? per_cu * std::max(main_ns, epi_ns) + lat + std::min(main_ns, epi_ns)
@@ -875,10 +875,10 @@ bool img_candidate(const ConvGeom& g, const GemmArgs& ga, int kt, int st, int R,
 // keeps them: ksplit workgroups per wide tile each reduce a share of the stages into a partial
 // record (NCHW int32), and a second pass with small tiles (R = 32, enough workgroups for the
 // chip) sums the partials and runs the block epilogue.
-bool img_split_candidate(const ConvGeom& g, const GemmArgs& ga, int kt, int st, int R, int ipt, int CC, bool two,
+bool img_split_candidate(const ConvGeom& g, const ConvTraits& t, int kt, int st, int R, int ipt, int CC, bool two,
                          int ksplit, ImgPlan* out) {
   ImgPlan pa{}, pb{}, best_b{};
-  if (!img_candidate(g, ga, kt, st, R, ipt, CC, two, 1, &pa, 1, ksplit)) return false;
+  if (!img_candidate(g, t, kt, st, R, ipt, CC, two, 1, &pa, 1, ksplit)) return false;
   if (pa.ct > 4) return false;  // (the split kernels are instantiated for 2 and 4 column tiles per wave)
   const int tiles = pa.a.wgs, wgs = tiles * ksplit;
   if (tiles > 256 || wgs > 2048) return false;  // the plain plans already fill the chip
@@ -889,7 +889,7 @@ bool img_split_candidate(const ConvGeom& g, const GemmArgs& ga, int kt, int st, 
   bool have_b = false;
   for (int ipt_b = std::max(1, std::min(kImgMaxCols / hw, g.N)); ipt_b >= 1; --ipt_b)
     for (int two_b = 1; two_b >= 0; --two_b)
-      if (g.O % 32 == 0 && img_candidate(g, ga, kt, st, 32, ipt_b, 32, two_b, 1, &pb, 2, ksplit) && pb.ct <= 4 &&
+      if (g.O % 32 == 0 && img_candidate(g, t, kt, st, 32, ipt_b, 32, two_b, 1, &pb, 2, ksplit) && pb.ct <= 4 &&
           (!have_b || pb.cost < best_b.cost)) {
         best_b = pb;
         have_b = true;
@@ -910,7 +910,7 @@ bool img_split_candidate(const ConvGeom& g, const GemmArgs& ga, int kt, int st, 
 
 namespace {
 
-std::vector<ImgPlan> img_plans_build(const ConvGeom& g, const tk_conv2d_attrs* a, const GemmArgs& ga,
+std::vector<ImgPlan> img_plans_build(const ConvGeom& g, const tk_conv2d_attrs* a, const ConvTraits& t,
                                      bool have_chunked);
 
 // Every image-tile plan that applies to the conv block, in enumeration order (R, stage width,
@@ -921,7 +921,7 @@ std::vector<ImgPlan> img_plans_build(const ConvGeom& g, const tk_conv2d_attrs* a
 // find step's event-timed launches, which made every image plan of those blocks look 2x slower.
 using ImgPlans = std::shared_ptr<const std::vector<ImgPlan>>;
 
-ImgPlans img_plans(const ConvGeom& g, const tk_conv2d_attrs* a, const GemmArgs& ga, bool have_chunked) {
+ImgPlans img_plans(const ConvGeom& g, const tk_conv2d_attrs* a, const ConvTraits& t, bool have_chunked) {
   // Outside the ablation build tune_env() is compiled to nullptr (tk_conv.h), so every TK_IMG*
   // knob read by img_plans_build / img_candidate / conv_img_split_scratch_bytes is its constant
   // default and the geometry is the whole key.  The ablation build (plans follow TK_IMG_*
@@ -938,8 +938,7 @@ ImgPlans img_plans(const ConvGeom& g, const tk_conv2d_attrs* a, const GemmArgs& 
   const std::array<int64_t, 27> key = {g.N, g.C, g.H, g.W, g.O, g.KH, g.KW, g.OH, g.OW, g.cin_pad, g.k_pad,
                                        g.rows_pad, a->strides[0], a->strides[1], a->padding[0], a->padding[1],
                                        a->padding[2], a->padding[3], a->dilation[0], a->dilation[1],
-                                       ga.bias_out != nullptr, ga.RB != nullptr, ga.zA_vec != nullptr, ga.zA,
-                                       ga.has_add, ga.in_pix, have_chunked};
+                                       t.block, t.patch, t.zw_vec, t.zw, t.has_add, t.in_pix, have_chunked};
   static std::mutex mu;
   static std::map<std::pair<std::array<int64_t, 27>, std::string>, ImgPlans> cache;
   const auto ck = std::make_pair(key, knobs);
@@ -948,18 +947,18 @@ ImgPlans img_plans(const ConvGeom& g, const tk_conv2d_attrs* a, const GemmArgs& 
     auto it = cache.find(ck);
     if (it != cache.end()) return it->second;
   }
-  ImgPlans plans = std::make_shared<const std::vector<ImgPlan>>(img_plans_build(g, a, ga, have_chunked));
+  ImgPlans plans = std::make_shared<const std::vector<ImgPlan>>(img_plans_build(g, a, t, have_chunked));
   std::lock_guard<std::mutex> lock(mu);
   if (cache.size() > 4096) cache.clear();
   cache.emplace(ck, plans);
   return plans;
 }
 
-std::vector<ImgPlan> img_plans_build(const ConvGeom& g, const tk_conv2d_attrs* a, const GemmArgs& ga,
+std::vector<ImgPlan> img_plans_build(const ConvGeom& g, const tk_conv2d_attrs* a, const ConvTraits& t,
                                      bool have_chunked) {
   std::vector<ImgPlan> out;
-  if (!env_int("TK_IMG", 1) || !ga.bias_out) return out;  // conv blocks only
-  if (ga.RB || ga.zA_vec || ga.zA != 0) return out;       // the weights' zero point must be 0
+  if (!env_int("TK_IMG", 1) || !t.block) return out;  // conv blocks only
+  if (t.patch) return out;                            // the weights' zero point must be 0
   if (a->dilation[0] != 1 || a->dilation[1] != 1) return out;
   const int st = a->strides[0];
   if (a->strides[1] != st || (st != 1 && st != 2)) return out;
@@ -988,7 +987,7 @@ std::vector<ImgPlan> img_plans_build(const ConvGeom& g, const tk_conv2d_attrs* a
         for (int two = 0; two < 2; ++two) {
           if ((two && !two_mode) || (!two && two_mode == 2)) continue;
           for (int npass : {1, 2, 4})
-            if (img_candidate(g, ga, kt, st, R, ipt, CC, two, npass, &c)) out.push_back(c);
+            if (img_candidate(g, t, kt, st, R, ipt, CC, two, npass, &c)) out.push_back(c);
         }
       }
     }
@@ -1003,7 +1002,7 @@ std::vector<ImgPlan> img_plans_build(const ConvGeom& g, const tk_conv2d_attrs* a
           if ((kt == 3 && CC > 64) || g.cin_pad % CC || (force_cc && CC != force_cc)) continue;
           for (int ipt = std::min(maxcols / hw, g.N); ipt >= 1; --ipt)
             for (int two = 0; two < 2; ++two)
-              if (img_split_candidate(g, ga, kt, st, R, ipt, CC, two, S, &c)) out.push_back(c);
+              if (img_split_candidate(g, t, kt, st, R, ipt, CC, two, S, &c)) out.push_back(c);
         }
       }
   return out;
@@ -1011,9 +1010,9 @@ std::vector<ImgPlan> img_plans_build(const ConvGeom& g, const tk_conv2d_attrs* a
 
 }  // namespace
 
-int conv_img_algos(const ConvGeom& g, const tk_conv2d_attrs* a, const GemmArgs& ga, bool have_chunked,
+int conv_img_algos(const ConvGeom& g, const tk_conv2d_attrs* a, const ConvTraits& t, bool have_chunked,
                    int32_t* algos, int max_algos) {
-  const ImgPlans pp = img_plans(g, a, ga, have_chunked);
+  const ImgPlans pp = img_plans(g, a, t, have_chunked);
   const std::vector<ImgPlan>& plans = *pp;
   std::vector<int> order(plans.size());
   for (size_t i = 0; i < order.size(); ++i) order[i] = (int)i;
@@ -1035,9 +1034,9 @@ int conv_img_algos(const ConvGeom& g, const tk_conv2d_attrs* a, const GemmArgs& 
   return (int)plans.size();
 }
 
-int conv_img_describe(const ConvGeom& g, const tk_conv2d_attrs* a, const GemmArgs& ga, bool have_chunked, int algo,
+int conv_img_describe(const ConvGeom& g, const tk_conv2d_attrs* a, const ConvTraits& t, bool have_chunked, int algo,
                       char* buf, int len) {
-  const ImgPlans pp = img_plans(g, a, ga, have_chunked);
+  const ImgPlans pp = img_plans(g, a, t, have_chunked);
   const std::vector<ImgPlan>& plans = *pp;
   const int i = algo - kAlgoImg0;
   if (i < 0 || i >= (int)plans.size()) return TK_ERR_INVALID_ARG;
@@ -1074,10 +1073,10 @@ static int set_lds(ImgKernel kern, size_t lds, int* rc) {
   return 0;
 }
 
-int conv_img_try(const ConvGeom& g, const tk_conv2d_attrs* a, const GemmArgs& ga, const int8_t* chunked, void* scratch,
-                 int algo, hipStream_t s, int* rc) {
+int conv_img_try(const ConvGeom& g, const tk_conv2d_attrs* a, const ConvTraits& t, const GemmArgs& ga,
+                 const int8_t* chunked, void* scratch, int algo, hipStream_t s, int* rc) {
   if (algo == kAlgoIm2col || algo == kAlgoPf2 || algo == kAlgoPf3) return 0;
-  const ImgPlans pp = img_plans(g, a, ga, chunked != nullptr);
+  const ImgPlans pp = img_plans(g, a, t, chunked != nullptr);
   const std::vector<ImgPlan>& plans = *pp;
   if (plans.empty() && algo == 0) return 0;
   if (plans.empty() || (algo >= kAlgoImg0 && algo - kAlgoImg0 >= (int)plans.size()) ||

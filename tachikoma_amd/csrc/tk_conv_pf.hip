@@ -393,12 +393,11 @@ int cu_count() {
 }
 }  // namespace
 
-bool conv_pf_applies(const ConvGeom& g, const GemmArgs& ga) {
+bool conv_pf_applies(const ConvGeom& g, const ConvTraits& t) {
   const int64_t hw = (int64_t)g.OH * g.OW;
-  return ga.fast_epi != 0 && ga.unitap && ga.RB == nullptr && ga.zB_vec == nullptr && ga.ch_is_row && ga.out_nchw &&
-         hw % 4 == 0 && hw > 64 && g.k_pad % kBK == 0 && g.KH * g.KW <= 64 &&
-         (int64_t)(g.cin_pad / 16) * ga.in_pix * 16 < (1ll << 40) &&
-         (ga.shadow_out == nullptr || (int64_t)(ga.shadow_cpad / 16) * g.N * g.OH * g.OW * 16 < 0xFFFFFF00ll);
+  return t.fast_epi != 0 && t.unitap && !t.patch && hw % 4 == 0 && hw > 64 && g.k_pad % kBK == 0 && g.KH * g.KW <= 64 &&
+         (int64_t)(g.cin_pad / 16) * t.in_pix * 16 < (1ll << 40) &&
+         (!t.shadow || (int64_t)(t.shadow_cpad / 16) * g.N * g.OH * g.OW * 16 < 0xFFFFFF00ll);
 }
 
 int conv_pf_run(const ConvGeom& g, GemmArgs ga, int ring, hipStream_t s) {

@@ -197,10 +197,10 @@ __global__ __launch_bounds__(64) void dense_slices_epilogue_kernel(GemmArgs g, i
 
 }  // namespace
 
-bool conv_dense_applies(const ConvGeom& g, const GemmArgs& ga) {
+bool conv_dense_applies(const ConvGeom& g, const ConvTraits& t) {
   // (K steps of 32 bytes cover exactly the shadow's channel groups: cin_pad % 32 == 0)
-  return g.H == 1 && g.W == 1 && g.KH == 1 && g.KW == 1 && g.OH == 1 && g.OW == 1 && ga.zA == 0 && !ga.zA_vec &&
-         !ga.RB && !ga.has_add && g.cin_pad % 32 == 0 && g.N <= 1024;
+  return g.H == 1 && g.W == 1 && g.KH == 1 && g.KW == 1 && g.OH == 1 && g.OW == 1 && !t.patch && !t.has_add &&
+         g.cin_pad % 32 == 0 && g.N <= 1024;
 }
 
 int64_t conv_dense_scratch_bytes(const ConvGeom& g) {
@@ -209,8 +209,8 @@ int64_t conv_dense_scratch_bytes(const ConvGeom& g) {
              ? (int64_t)kDenseMaxSlices * g.N * g.O * 4 : 0;
 }
 
-int conv_dense_run(const ConvGeom& g, const GemmArgs& ga, void* scratch, hipStream_t s) {
-  TK_CHECK_ARG(conv_dense_applies(g, ga), "dense tile kernel: not a [B, K] x [U, K]^T block with zero weight zero point");
+int conv_dense_run(const ConvGeom& g, const ConvTraits& t, const GemmArgs& ga, void* scratch, hipStream_t s) {
+  TK_CHECK_ARG(conv_dense_applies(g, t), "dense tile kernel: not a [B, K] x [U, K]^T block with zero weight zero point");
   TK_CHECK_ARG(ga.RA || ga.zB == 0, "dense tile kernel: weight sums needed for the input zero point");
   TK_CHECK_ARG(ga.k_pad <= ga.lda && (int64_t)(g.O + 31) / 32 * 32 <= g.rows_pad, "dense tile kernel: packed weight rows");
   const int ksteps = g.cin_pad / 32;

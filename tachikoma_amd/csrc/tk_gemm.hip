@@ -14,64 +14,18 @@
 // where out-of-bounds taps hold a' = za on real channels (they contribute 0,
 // python/tvm/relay/qnn/op/legalizations.py:195-226 pads with zeros after the shift).
 // The epilogue writes int32 NCHW directly (lanes run along pixels: coalesced).
+//
+// This file holds gemm_i8_kernel, the table from a variant key (tk_conv_plan.h) to its
+// instantiation, and the dense path.  The conv host code is tk_conv.cc, operand preparation
+// tk_conv_prep.hip.
 #include <algorithm>
-#include <cstdio>
-#include <mutex>
+#include <string>
 #include <type_traits>
-#include <climits>
-#include <cstdlib>
-#include <cstring>
 
 #include "tk_conv.h"
 #include "tk_ops.h"
 
 namespace tk {
-
-// Writes one element of every output of a fused block.  Mirrors, per element:
-// nn.bias_add (int32 wrap), RequantizeLowerInt + clip/cast to the out dtype
-// (src/relay/qnn/op/requantize.cc:195-273), then clip (python/tvm/topi/math.py:615-640).
-template <bool kBlock>
-__device__ __forceinline__ void epilogue_store(const GemmArgs& g, int64_t off, int ch, int64_t pix, uint32_t v) {
-  g.C[off] = (int32_t)v;
-  if (!kBlock) return;
-  const BlockConsts c = block_consts(g.bias, g.rq, ch);
-  v += (uint32_t)c.bias;
-  g.bias_out[off] = (int32_t)v;
-  const int32_t q = block_rq<false>(v, (uint32_t)c.zp, c.m, c.s, g.rq.mode, g.rq.zp_out, (int32_t)g.rq.qmin, (int32_t)g.rq.qmax);
-  g.rq_out[off] = (uint8_t)q;
-  int32_t last = q;
-  if (g.has_clip) {
-    last = block_clip(q, g.clip_lo, g.clip_hi);
-    g.clip_out[off] = (uint8_t)last;
-  }
-  if (g.shadow_out) {
-    g.shadow_out[((int64_t)(ch >> 4) * g.N + pix) * 16 + (ch & 15)] = (uint8_t)((uint32_t)last ^ g.shadow_xor);
-    if (ch == g.M - 1)  // the padded channels of the last group are written as 0
-      for (int c2 = ch + 1; c2 < g.shadow_cpad; ++c2) g.shadow_out[((int64_t)(c2 >> 4) * g.N + pix) * 16 + (c2 & 15)] = 0;
-  }
-}
-
-// record stores (nontemporal: see store_nt in tk_common.h)
-template <int V>
-__device__ __forceinline__ void st_i32(int32_t* dst, const int32_t* v, bool nt) {
-  if constexpr (V == 4) {
-    if (nt) __builtin_nontemporal_store(v4i{v[0], v[1], v[2], v[3]}, reinterpret_cast<v4i*>(dst));
-    else *reinterpret_cast<v4i*>(dst) = v4i{v[0], v[1], v[2], v[3]};
-  } else {
-    *dst = v[0];  // partial lines: let L2 merge them
-  }
-}
-
-template <int V>
-__device__ __forceinline__ void st_i8(uint8_t* dst, const int32_t* v, bool nt) {
-  if constexpr (V == 4) {
-    const uint32_t w = pack4u(v[0], v[1], v[2], v[3]);
-    if (nt) __builtin_nontemporal_store(w, reinterpret_cast<uint32_t*>(dst));
-    else *reinterpret_cast<uint32_t*>(dst) = w;
-  } else {
-    *dst = (uint8_t)v[0];
-  }
-}
 
 // V consecutive columns of one row after zero-point folding: stores each record as
 // soon as it is complete, transforming v in place (conv → bias_add → requantize →
@@ -1100,1002 +1054,37 @@ gemm_i8_kernel(GemmArgs g) {
   }
 }
 
-// ---------------------------------------------------------------- operand preparation
+// ---------------------------------------------------------------- launch by variant key
 
-// pack OIHW (int8/uint8) -> [Cout_rows][k_pad], k = (kh*KW + kw)*cin_pad + c ; row sums over real taps.
-// groups == 1 only (grouped convs take the direct kernel).
-__global__ __launch_bounds__(256) void pack_weight_kernel(const int8_t* __restrict__ w, int8_t* __restrict__ packed,
-                                                          int32_t* __restrict__ sums, int Cout, int Cin, int KH, int KW,
-                                                          int cin_pad, int k_pad, int xor_u8) {
-  int o = blockIdx.x;
-  int8_t* dst = packed + (int64_t)o * k_pad;
-  int32_t s = 0;
-  for (int k = threadIdx.x; k < k_pad; k += blockDim.x) {
-    int tap = k / cin_pad;
-    int c = k - tap * cin_pad;
-    int8_t v = 0;
-    if (o < Cout && tap < KH * KW && c < Cin) {
-      int kh = tap / KW, kw = tap - (tap / KW) * KW;
-      uint8_t raw = (uint8_t)w[(((int64_t)o * Cin + c) * KH + kh) * KW + kw];
-      v = (int8_t)(xor_u8 ? (raw ^ 0x80) : raw);
-      s += v;
-    }
-    dst[k] = v;
-  }
-  __shared__ int32_t red[256];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0 && o < Cout) sums[o] = red[0];
-}
-
-// NCHW int8/uint8 -> shadow [cin_pad/16][N*HW][16]; padded channels 0; uint8 xor 0x80.
-// One thread per (16-channel chunk, pixel); lanes run along pixels, so each channel
-// plane read is a contiguous 64-byte span and the 16-byte stores are contiguous.
-__global__ __launch_bounds__(256) void shadow_kernel(const uint8_t* __restrict__ x, uint8_t* __restrict__ y, int N,
-                                                     int C, int HW, int cin_pad, int xor_u8) {
-  int chunks = cin_pad / 16;
-  int64_t total = (int64_t)N * HW * chunks;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += stride) {
-    int64_t q = t / HW;          // (n, chunk)
-    int pix = (int)(t - q * HW);
-    int chunk = (int)(q % chunks);
-    int n = (int)(q / chunks);
-    uint8_t v[16];
-    const uint8_t* src = x + ((int64_t)n * C) * HW + pix;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      int c = chunk * 16 + j;
-      uint8_t b = 0;
-      if (c < C) b = xor_u8 ? (uint8_t)(src[(int64_t)c * HW] ^ 0x80) : src[(int64_t)c * HW];
-      v[j] = b;
-    }
-    __builtin_memcpy(y + ((int64_t)chunk * N * HW + (int64_t)n * HW + pix) * 16, v, 16);
-  }
-}
-
-// dense data [M][K] -> [M_rows][k_pad] (zero padded, uint8 xor 0x80) + row sums.
-__global__ __launch_bounds__(256) void pad_rows_kernel(const uint8_t* __restrict__ x, int8_t* __restrict__ y,
-                                                       int32_t* __restrict__ sums, int M, int K, int k_pad, int xor_u8) {
-  int m = blockIdx.x;
-  int32_t s = 0;
-  for (int k = threadIdx.x; k < k_pad; k += blockDim.x) {
-    int8_t v = 0;
-    if (m < M && k < K) {
-      uint8_t raw = x[(int64_t)m * K + k];
-      v = (int8_t)(xor_u8 ? (raw ^ 0x80) : raw);
-      s += v;
-    }
-    y[(int64_t)m * k_pad + k] = v;
-  }
-  __shared__ int32_t red[256];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0 && m < M && sums) sums[m] = red[0];
-}
-
-// Σ over the real taps/channels of the (zero-point-filled) patch of every output pixel:
-// only needed when the kernel zero point is non-zero.
-__global__ __launch_bounds__(256) void patch_sum_kernel(const int8_t* __restrict__ shadow, int32_t* __restrict__ out,
-                                                        GemmArgs g, int Cin) {
-  int64_t total = g.N;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  int8_t zpa = (int8_t)(g.fill & 0xFF);
-  for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < total; p += stride) {
-    int hw = g.OH * g.OW;
-    int img = (int)(p / hw);
-    int rem = (int)(p - (int64_t)img * hw);
-    int oh = rem / g.OW, ow = rem - (rem / g.OW) * g.OW;
-    int32_t s = 0;
-    for (int kh = 0; kh < g.KH; ++kh) {
-      int ih = oh * g.sh - g.pt + kh * g.dh;
-      for (int kw = 0; kw < g.KW; ++kw) {
-        int iw = ow * g.sw - g.pl + kw * g.dw;
-        if (ih < 0 || ih >= g.H || iw < 0 || iw >= g.W) {
-          s += (int32_t)zpa * Cin;
-        } else {
-          const int64_t pix = ((int64_t)img * g.H + ih) * g.W + iw;
-          for (int c = 0; c < Cin; ++c) s += shadow[((int64_t)(c >> 4) * g.in_pix + pix) * 16 + (c & 15)];
-        }
-      }
-    }
-    out[p] = s;
-  }
-}
-
-// Direct (VALU) grouped / depthwise / tiny-channel convolution on NCHW int8/uint8.
-// out[n][o][oh][ow] = Σ_{c in group(o), r, s} (a - za)(w - zw[o]); padded taps contribute 0.
-template <typename Tx, typename Tw, bool kBlock>
-__global__ __launch_bounds__(256) void direct_conv_kernel(const Tx* __restrict__ x, const Tw* __restrict__ w,
-                                                          int N, int C, int H, int W, int O,
-                                                          int OH, int OW, int KH, int KW, int sh, int sw, int pt, int pl,
-                                                          int dh, int dw, int groups, int32_t za, int32_t zw,
-                                                          const int32_t* __restrict__ zw_vec, GemmArgs g) {
-  int64_t total = (int64_t)N * O * OH * OW;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  int cg = C / groups, og = O / groups;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += stride) {
-    int ow = (int)(i % OW);
-    int64_t t = i / OW;
-    int oh = (int)(t % OH);
-    t /= OH;
-    int o = (int)(t % O);
-    int n = (int)(t / O);
-    int grp = o / og;
-    int32_t zwo = zw_vec ? zw_vec[o] : zw;
-    uint32_t acc = 0;
-    for (int c = 0; c < cg; ++c) {
-      int ci = grp * cg + c;
-      const Tx* plane = x + ((int64_t)n * C + ci) * H * W;
-      const Tw* wk = w + (((int64_t)o * cg + c) * KH) * KW;
-      for (int r = 0; r < KH; ++r) {
-        int ih = oh * sh - pt + r * dh;
-        if (ih < 0 || ih >= H) continue;
-        for (int s = 0; s < KW; ++s) {
-          int iw = ow * sw - pl + s * dw;
-          if (iw < 0 || iw >= W) continue;
-          int32_t a = (int32_t)plane[ih * W + iw] - za;
-          int32_t b = (int32_t)wk[r * KW + s] - zwo;
-          acc += (uint32_t)(a * b);
-        }
-      }
-    }
-    int64_t pix = (int64_t)n * OH * OW + (int64_t)oh * OW + ow;
-    epilogue_store<kBlock>(g, i, o, pix, acc);
-  }
-}
-
-// Depthwise 3x3 conv (groups == C == O, the MobileNetV2 layers) with the fused block epilogue.
-// One workgroup = one image x 16 channels x a band of BH output rows:
-//   * the input band plus halo is staged planar in LDS ([16][rows][cols], bytes, taps outside
-//     the image hold the input zero point so they contribute 0, legalizations.py:195-226), the
-//     per-channel weights minus their zero point as int32;
-//   * lanes run along output columns, V consecutive pixels each, so every record store is a
-//     contiguous row segment of an NCHW plane (b128 int32 / b32 int8 when V = 4);
-//   * the final 8-bit values are parked in LDS and written to the next conv's channel-blocked
-//     shadow as one 16-byte chunk (the 16 channels) per pixel.
-// Same arithmetic as direct_conv_kernel / epilogue_store (int32 wrap-around accumulation).
-template <typename Tx, typename Tw, int V>
-__global__ __launch_bounds__(256) void dw3x3_kernel(const Tx* __restrict__ x, const Tw* __restrict__ w, int C, int H,
-                                                    int W, int OH, int OW, int sh, int sw, int pt, int pl, int32_t za,
-                                                    int32_t zw, const int32_t* __restrict__ zw_vec, int BH, int bands,
-                                                    int Wp, GemmArgs g) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t dsm[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int bid = blockIdx.x;
-  const int band = bid % bands;
-  bid /= bands;
-  const int cgroups = C / 16;
-  const int cgrp = bid % cgroups, n = bid / cgroups;
-  const int c0 = cgrp * 16;
-  const int oh0 = band * BH;
-  const int bh = min(BH, OH - oh0);
-  const int rows_in = (bh - 1) * sh + 3;
-  const int ih0 = oh0 * sh - pt;
-  uint8_t* tin = dsm;
-  const int tin_bytes = (16 * rows_in * Wp + 15) & ~15;
-  int32_t* wts = reinterpret_cast<int32_t*>(dsm + tin_bytes);
-  uint8_t* tout = dsm + tin_bytes + 16 * 9 * 4;
-  // ---- stage the band: (channel, input row) rows of Wp = W + 8 bytes, input column iw at
-  // byte 4 + iw (4-byte aligned interior; the 4-byte halos hold the zero point); one dword
-  // per lane (W % 4 == 0, W <= 248), 8 rows per wave at a time so that 8 loads are in flight
-  const uint32_t fill4 = 0x01010101u * (uint8_t)za;
-  const int nrows = 16 * rows_in;
-  const int words = W / 4;
-  for (int r0 = wave; r0 < nrows; r0 += 32) {
-    uint32_t v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int r = r0 + 4 * u;
-      const int c = r / rows_in, lr = r - c * rows_in;
-      const int ih = ih0 + lr;
-      const bool ok = r < nrows && ih >= 0 && ih < H && lane < words;
-      const uint32_t* src = reinterpret_cast<const uint32_t*>(
-          reinterpret_cast<const uint8_t*>(x) + (((int64_t)n * C + c0 + c) * H + (ok ? ih : 0)) * W);
-      v[u] = ok ? src[lane] : fill4;
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int r = r0 + 4 * u;
-      if (r < nrows) {
-        uint32_t* row = reinterpret_cast<uint32_t*>(tin + r * Wp);
-        if (lane < words) row[1 + lane] = v[u];
-        else if (lane == words) row[0] = fill4, row[1 + words] = fill4;
-      }
-    }
-  }
-  if (tid < 16 * 9) {
-    const int c = tid / 9;
-    wts[tid] = (int32_t)w[(int64_t)(c0 + c) * 9 + (tid - c * 9)] - (zw_vec ? zw_vec[c0 + c] : zw);
-  }
-  __syncthreads();
-  // ---- 9 taps + epilogue, V pixels of one channel row per item
-  const int owv = OW / V;
-  const int items = 16 * bh * owv;
-  const int qmin = (int)g.rq.qmin, qmax = (int)g.rq.qmax;
-  for (int it = tid; it < items; it += 256) {
-    const int vv = it % owv;
-    const int t = it / owv;
-    const int row = t % bh, c = t / bh;
-    const int ch = c0 + c;
-    int32_t acc[V];
-#pragma unroll
-    for (int e = 0; e < V; ++e) acc[e] = 0;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      const uint8_t* base = tin + (c * rows_in + row * sh + r) * Wp;
-#pragma unroll
-      for (int s2 = 0; s2 < 3; ++s2) {
-        const int32_t wv = wts[c * 9 + r * 3 + s2];
-#pragma unroll
-        for (int e = 0; e < V; ++e) {
-          const int32_t a = (int32_t)(Tx)base[(vv * V + e) * sw + s2 + 4 - pl] - za;
-          acc[e] = (int32_t)((uint32_t)acc[e] + (uint32_t)(a * wv));
-        }
-      }
-    }
-    const int oh = oh0 + row, ow = vv * V;
-    const int64_t off = (((int64_t)n * C + ch) * OH + oh) * OW + ow;
-    int32_t v[V];
-#pragma unroll
-    for (int e = 0; e < V; ++e) v[e] = acc[e];
-    st_i32<V>(g.C + off, v, false);
-    const BlockConsts k = block_consts(g.bias, g.rq, ch);
-#pragma unroll
-    for (int e = 0; e < V; ++e) v[e] = (int32_t)((uint32_t)v[e] + (uint32_t)k.bias);
-    st_i32<V>(g.bias_out + off, v, false);
-#pragma unroll
-    for (int e = 0; e < V; ++e) v[e] = block_rq<false>((uint32_t)v[e], (uint32_t)k.zp, k.m, k.s, g.rq.mode, g.rq.zp_out, qmin, qmax);
-    st_i8<V>(g.rq_out + off, v, false);
-    if (g.has_clip) {
-#pragma unroll
-      for (int e = 0; e < V; ++e) v[e] = block_clip(v[e], g.clip_lo, g.clip_hi);
-      st_i8<V>(g.clip_out + off, v, false);
-    }
-#pragma unroll
-    for (int e = 0; e < V; ++e) tout[((row * OW) + ow + e) * 16 + c] = (uint8_t)((uint32_t)v[e] ^ g.shadow_xor);
-  }
-  if (!g.shadow_out) return;
-  __syncthreads();
-  // ---- shadow: 16 channels of one pixel per 16-byte store, contiguous across lanes
-  const int64_t pix0 = ((int64_t)n * OH + oh0) * OW;
-  for (int p = tid; p < bh * OW; p += 256)
-    *reinterpret_cast<v4i*>(g.shadow_out + ((int64_t)cgrp * g.N + pix0 + p) * 16) =
-        *reinterpret_cast<const v4i*>(tout + p * 16);
-}
-
-// ---------------------------------------------------------------- host wrappers
-
-
-// tk_dw.hip: the depthwise 3x3 tile kernel (returns 1 and sets *rc when its plan applies)
-int dw_block_try(const tk_tensor* data, const tk_tensor* weight, const ConvGeom& g, const tk_conv2d_attrs* a,
-                 const GemmArgs& ga, hipStream_t s, int* rc);
-
-static int conv_geom(const tk_tensor* data, const tk_tensor* weight, const tk_conv2d_attrs* a, ConvGeom* g) {
-  if (data->ndim != 4 || weight->ndim != 4) return TK_ERR_SHAPE;
-  g->N = (int)data->shape[0];
-  g->C = (int)data->shape[1];
-  g->H = (int)data->shape[2];
-  g->W = (int)data->shape[3];
-  g->O = (int)weight->shape[0];
-  g->KH = (int)weight->shape[2];
-  g->KW = (int)weight->shape[3];
-  int groups = a ? a->groups : 1;
-  if (groups < 1 || g->C % groups || g->O % groups || weight->shape[1] * groups != g->C) return TK_ERR_SHAPE;
-  if (a) {
-    int dh = a->dilation[0], dw = a->dilation[1];
-    g->OH = (g->H + a->padding[0] + a->padding[2] - dh * (g->KH - 1) - 1) / a->strides[0] + 1;
-    g->OW = (g->W + a->padding[1] + a->padding[3] - dw * (g->KW - 1) - 1) / a->strides[1] + 1;
-  }
-  g->cin_pad = (g->C + 15) / 16 * 16;
-  int k = g->KH * g->KW * g->cin_pad;
-  g->k_pad = (k + kBK - 1) / kBK * kBK;
-  g->k_eff = g->KH * g->KW * g->C;
-  g->rows_pad = (g->O + 127) / 128 * 128;
-  return TK_OK;
-}
-
-static bool use_mfma_conv(const ConvGeom& g, int groups) { return groups == 1 && g.O >= 16 && g.C >= 3; }
-
-int64_t conv_packed_weight_bytes(const tk_tensor* weight, int groups) {
-  if (!weight || weight->ndim != 4 || groups != 1) return 0;
-  int O = (int)weight->shape[0], C = (int)weight->shape[1], KH = (int)weight->shape[2], KW = (int)weight->shape[3];
-  int cin_pad = (C + 15) / 16 * 16;
-  int64_t k_pad = ((int64_t)KH * KW * cin_pad + kBK - 1) / kBK * kBK;
-  int64_t rows = (O + 127) / 128 * 128;
-  // + the chunked image of a KHxKW > 1 weight for the image-tile kernel (tk_conv_img.hip)
-  return rows * k_pad + conv_img_chunked_bytes((int)rows, cin_pad, KH * KW);
-}
-
-int conv_pack_weight(const tk_tensor* weight, int groups, void* packed, int32_t* sums, hipStream_t s) {
-  TK_CHECK_ARG(weight && packed && sums && weight->ndim == 4 && groups == 1, "bad arguments");
-  TK_CHECK_ARG(is_int8ish(weight), "weight must be int8/uint8");
-  int O = (int)weight->shape[0], C = (int)weight->shape[1], KH = (int)weight->shape[2], KW = (int)weight->shape[3];
-  int cin_pad = (C + 15) / 16 * 16;
-  int k_pad = (KH * KW * cin_pad + kBK - 1) / kBK * kBK;
-  int rows = (O + 127) / 128 * 128;
-  hipLaunchKernelGGL(pack_weight_kernel, dim3(rows), dim3(256), 0, s, (const int8_t*)ptr(weight), (int8_t*)packed, sums,
-                     O, C, KH, KW, cin_pad, k_pad, (int)is_uint(weight, 8));
-  TK_LAUNCH_CHECK();
-  return conv_img_pack(weight, (int8_t*)packed + (int64_t)rows * k_pad, rows, cin_pad, s);
-}
-
-int64_t conv_shadow_bytes(const tk_tensor* data) {
-  if (!data || data->ndim != 4) return 0;
-  int64_t cin_pad = (data->shape[1] + 15) / 16 * 16;
-  return data->shape[0] * data->shape[2] * data->shape[3] * cin_pad;
-}
-
-int make_shadow_impl(const tk_tensor* data, void* shadow, hipStream_t s) {
-  TK_CHECK_ARG(data && shadow && data->ndim == 4 && is_int8ish(data), "data must be 4-D int8/uint8");
-  int N = (int)data->shape[0], C = (int)data->shape[1], HW = (int)(data->shape[2] * data->shape[3]);
-  int cin_pad = (C + 15) / 16 * 16;
-  int64_t total = (int64_t)N * HW * (cin_pad / 16);
-  int grid = (int)std::min<int64_t>((total + 255) / 256, 2048);
-  hipLaunchKernelGGL(shadow_kernel, dim3(std::max(grid, 1)), dim3(256), 0, s, (const uint8_t*)ptr(data),
-                     (uint8_t*)shadow, N, C, HW, cin_pad, (int)is_uint(data, 8));
-  TK_LAUNCH_CHECK();
-  return TK_OK;
-}
-
-static inline uint32_t rep4(int v) {
-  uint32_t b = (uint8_t)(int8_t)v;
-  return b | (b << 8) | (b << 16) | (b << 24);
-}
-
-
-// Validates a fused block and fills the epilogue part of GemmArgs.
-static int setup_block(GemmArgs& ga, const BlockIO* b, const tk_tensor* conv_out, int channels, int ch_axis) {
-  if (!b) return TK_OK;
-  const tk_block_attrs* at = b->attrs;
-  TK_CHECK_ARG(at && b->outs && b->bias, "block needs bias, attrs and outputs");
-  const int has_add = at->has_add ? 1 : 0;
-  TK_CHECK_ARG(b->n_outs == 3 + has_add + (at->has_clip ? 1 : 0), "outs = {conv, bias_add, requantize, [add], [clip]}");
-  TK_CHECK_ARG(is_int(b->bias, 32) && numel(b->bias) == channels, "bias must be int32 [channels]");
-  const tk_tensor* bo = b->outs[1];
-  const tk_tensor* rq = b->outs[2];
-  TK_CHECK_ARG(is_int(bo, 32) && numel(bo) == numel(conv_out), "bias_add output must be int32, conv shaped");
-  TK_CHECK_ARG(is_int8ish(rq) && numel(rq) == numel(conv_out), "requantize output must be int8/uint8, conv shaped");
-  int rq_axis = at->requantize.axis;
-  TK_CHECK_ARG(rq_axis == ch_axis || at->requantize.mode <= TK_RQ_TENSOR_TONEAREST,
-               "requantize must run along the channel axis to fuse");
-  for (int k = 3; k < b->n_outs; ++k)
-    TK_CHECK_ARG(b->outs[k]->dtype.code == rq->dtype.code && b->outs[k]->dtype.bits == 8 &&
-                     numel(b->outs[k]) == numel(conv_out) && compact(b->outs[k]),
-                 "add / clip outputs must match the requantize output");
-  if (has_add) {
-    const tk_tensor* res = at->residual;
-    TK_CHECK_ARG(res && dt_of(res) == dt_of(rq) && numel(res) == numel(conv_out) && compact(res),
-                 "residual must match the requantize output (same shape and dtype)");
-    TK_CHECK_ARG(at->add.lhs.mode <= TK_RQ_TENSOR_TONEAREST && at->add.rhs.mode <= TK_RQ_TENSOR_TONEAREST,
-                 "qnn.add: per-tensor parameters only");
-    const tk_requantize_attrs& blk_side = at->block_is_rhs ? at->add.rhs : at->add.lhs;
-    const tk_requantize_attrs& res_side = at->block_is_rhs ? at->add.lhs : at->add.rhs;
-    auto rqp = [](const tk_requantize_attrs& r) {
-      RqParams q{};
-      q.mode = r.mode;
-      q.multiplier = r.multiplier;
-      q.shift = r.shift;
-      q.zp_in = r.input_zero_point;
-      q.zp_out = r.output_zero_point;
-      q.inner = 1;
-      q.C = 1;
-      return q;
-    };
-    ga.has_add = 1;
-    ga.add_res = (const uint8_t*)ptr(res);
-    ga.add_out = (uint8_t*)ptr(b->outs[3]);
-    ga.add_pb = rqp(blk_side);
-    ga.add_pr = rqp(res_side);
-    ga.add_up_b = at->block_is_rhs ? at->add.rhs_upcast : at->add.lhs_upcast;
-    ga.add_up_r = at->block_is_rhs ? at->add.lhs_upcast : at->add.rhs_upcast;
-    ga.add_zp = at->add.output_zero_point;
-  }
-  ga.bias = (const int32_t*)ptr(b->bias);
-  ga.bias_out = (int32_t*)ptr(bo);
-  ga.rq_out = (uint8_t*)ptr(rq);
-  ga.clip_out = at->has_clip ? (uint8_t*)ptr(b->outs[3 + has_add]) : nullptr;
-  ga.has_clip = at->has_clip;
-  bool u8 = is_uint(rq, 8);
-  int64_t lo = u8 ? 0 : -128, hi = u8 ? 255 : 127;
-  ga.clip_lo = (int32_t)std::max(at->clip_min, lo);
-  // clip is max(min(x, a_max), a_min) (topi/math.py:634-638): a_min wins when a_min > a_max, which
-  // the kernels' min(max(x, lo), hi) reproduces with hi raised to lo (and clamp_i32 needs lo <= hi)
-  ga.clip_hi = (int32_t)std::max<int64_t>(std::min(at->clip_max, hi), ga.clip_lo);
-  RqParams& p = ga.rq;
-  p.mode = at->requantize.mode;
-  p.multiplier = at->requantize.multiplier;
-  p.shift = at->requantize.shift;
-  p.zp_in = at->requantize.input_zero_point;
-  p.zp_out = at->requantize.output_zero_point;
-  p.ms = at->requantize.multipliers;
-  p.ss = at->requantize.shifts;
-  p.zps = at->requantize.input_zero_points;
-  p.inner = 1;
-  p.C = channels;
-  p.qmin = lo;
-  p.qmax = hi;
-  p.clip_out = 1;
-  if ((p.mode == TK_RQ_AXIS_UPWARD || p.mode == TK_RQ_AXIS_TONEAREST) && (!p.ms || !p.ss)) {
-    set_error("block: per-axis requantize needs device multipliers/shifts");
-    return TK_ERR_INVALID_ARG;
-  }
-  ga.shadow_out = (uint8_t*)b->shadow_out;
-  ga.shadow_cpad = (channels + 15) / 16 * 16;
-  ga.shadow_xor = u8 ? 0x80u : 0u;
-  return TK_OK;
-}
-
-// Tile order (tile_of): on planes of up to 28x28 outputs, each XCD takes a contiguous run of N
-// tiles, so the int32 record lines two neighbouring tiles share (rows of 784 B or less) are
-// completed in one L2; on larger planes N tiles are striped over the XCDs (the 56x56 stage
-// measured 5-7 % faster striped, the 28/14/7 stages 5-11 % faster chunked,
-// profiles/r01e_ab_xcd_order.txt).  TK_XCD overrides (0 = plain order).
-// Kernel-selection switches (TK_XCD, TK_RING, TK_FASTEPI, ...) exist for A/B measurements
-// only: they are read from the environment in the ablation build (build.py --ablation,
-// -DTK_ABLATION_BUILD, loaded by the tools through TK_LIB_PATH).  The product library
-// compiles them to their defaults, so no variable on a box changes what it runs.
-
-static int xcd_order(int64_t out_hw) {
-  const char* e = tune_env("TK_XCD");
-  return e ? atoi(e) : (out_hw <= 784 ? 2 : 1);
-}
-
-static int nt_stores() {
-  const char* e = tune_env("TK_NT");
-  return e ? atoi(e) : 1;
-}
-
-
-static int ring_depth() {
-  const char* e = tune_env("TK_RING");
-  const int r = e ? atoi(e) : 3;
-  return r >= 3 && r <= 5 ? r : 3;
-}
-
-static int ablate_flags() {
-  const char* e = tune_env("TK_ABLATE");
-  return e ? atoi(e) : 0;
-}
-
-// Split-K plan of an MFMA conv: layers whose tile grid cannot give every CU a workgroup
-// (the 7x7 stage at 64 samples) split the reduction so that ~3 workgroups per CU stay
-// resident (each split keeps >= 6 k-steps); kper = k-steps per split.
-struct SplitPlan {
-  int splits, kper;
-  int64_t tiles;
+namespace {
+struct GemmKernel {
+  GemmVariant key;
+  void (*fn)(GemmArgs);
 };
-// 64-row (MT = 1) tiles for conv blocks, except 128-channel layers with K >= 512, where one
-// 128-row tile (MT = 2) per N tile measured 7-18% faster (ResNet-50's 28x28 stage: the B
-// operand is staged once for both M halves); plain convs use MT = 2 above 64 channels.
-// The 256-channel 3x3 layers of the 14x14 stage (K = 2304) also take 128-row tiles while the grid
-// keeps >= 192 of them: half the im2col B re-reads per CU, -10 % (profiles/r02q_mt2_ab.txt).
-static bool conv_mt1(const ConvGeom& g, bool block) {
-  if (g.O <= 64) return true;
-  if (!block || tune_env("TK_MT2")) return false;
-  if (g.O == 128 && g.k_eff >= 512 && env_int("TK_MT2_128", 1)) return false;
-  const int64_t mt2_tiles = ((int64_t)g.N * g.OH * g.OW + 127) / 128 * ((g.O + 127) / 128);
-  return !(g.O == 256 && g.k_eff >= 2048 && mt2_tiles >= 192 && env_int("TK_MT2_256", 1));
-}
+#define TK_GEMM_ENTRY(MT, IM, BLK, MODE, RING, WIDE, BN) \
+  {GemmVariant{MT, IM, BLK, MODE, RING, WIDE, BN}, gemm_i8_kernel<MT, IM, BLK, MODE, RING, WIDE, BN>},
+const GemmKernel kGemmKernels[] = {TK_GEMM_VARIANTS(TK_GEMM_ENTRY)};
+#undef TK_GEMM_ENTRY
+}  // namespace
 
-static bool conv_needs_patch(const tk_tensor* weight, const tk_conv2d_attrs* a) {
-  return (a->kernel_zero_point - (is_uint(weight, 8) ? 128 : 0)) != 0 || a->kernel_zero_points;
-}
-
-static int conv_bn256_ipt(const ConvGeom& g, bool block, bool patch);
-
-// 256-column tiles over the flattened pixel axis (BN = 256, no image alignment) for the short-K,
-// >= 256-channel conv blocks on planes of more than 256 pixels (the 56x56 / 28x28 expand and
-// downsample layers): each store instruction writes one 1 KB segment of a channel row instead of
-// two 512-byte ones (store probe: -10 % on these layers' record writes,
-// profiles/r02j_store_patterns.txt "span 64x256").  Off (TK_BN256_ROWS=1 in the ablation build):
-// on the kernel the halved occupancy (2 workgroups per CU for 70 KB of LDS) costs more than the
-// store pattern gains, the 56x56 expand with its residual join +19 % (profiles/r02s_bn256_rows_ab.txt).
-static bool conv_bn256_rows(const ConvGeom& g, bool block, bool patch) {
-  const int64_t hw = (int64_t)g.OH * g.OW, P = (int64_t)g.N * hw;
-  if (!block || patch || hw <= 256 || hw % 4 != 0 || g.O < 256 || g.k_pad > 256 ||
-      P * g.O * 4 >= 0xFFFFFFC0ll || !env_int("TK_BN256_ROWS", 0))
-    return false;
-  return (P + 255) / 256 * ((g.O + 63) / 64) >= 256;
-}
-
-// Images per N tile of a conv block whose planes hold 1..64 pixels (0: plain 128-column
-// tiles).  Needs the flat epilogue's preconditions: no per-pixel zero-point patch, a channel
-// count that keeps every image run 16-byte aligned, and 32-bit record offsets.
-static int conv_image_tiles(const ConvGeom& g, bool block, bool patch) {
-  const int64_t hw = (int64_t)g.OH * g.OW;
-  if (const int ipt = conv_bn256_ipt(g, block, patch)) return ipt;
-  if (!block || patch || hw > 64 || g.O % 4 != 0 || (int64_t)g.N * hw * g.O * 4 >= 0xFFFFFFC0ll ||
-      !env_int("TK_IMGTILE", 1))
-    return 0;
-  return (int)(128 / hw);
-}
-
-static int64_t conv_ntiles(const ConvGeom& g, int ipt) {
-  return ipt ? ((int64_t)g.N + ipt - 1) / ipt : ((int64_t)g.N * g.OH * g.OW + 127) / 128;
-}
-
-// 256-column image tiles (BN = 256) for conv blocks whose planes hold 65..256 pixels (14x14):
-// floor(256 / HW) whole images per tile, so that each tile's records are contiguous runs
-// (probe: 2x the store rate of 128-column tiles that cross images on 14x14 planes,
-// profiles/r02j_store_patterns.txt).  Only where the grid still gives every CU a tile (no
-// split-K), with the flat epilogue's preconditions.  Returns images per tile, or 0.
-static int conv_bn256_ipt(const ConvGeom& g, bool block, bool patch) {
-  const int64_t hw = (int64_t)g.OH * g.OW;
-  // short reductions only (the store-bound expand layers): a long K loop at the one or two
-  // workgroups per CU of these tiles ran 15-20 % slower than 128-column tiles (3x3 256->256 and
-  // 1x1 1024->256 at 14x14, profiles/r02n_bn256_ab.txt)
-  if (!block || patch || hw <= 64 || hw > 256 || g.O % 4 != 0 || (int64_t)g.N * hw * g.O * 4 >= 0xFFFFFFC0ll ||
-      g.k_pad > env_int("TK_BN256_KMAX", 256) || !env_int("TK_BN256", 1))
-    return 0;
-  const int ipt = (int)(256 / hw);
-  const int64_t tiles = ((int64_t)g.N + ipt - 1) / ipt * ((g.O + 63) / 64);
-  return tiles >= 256 ? ipt : 0;
-}
-
-// Wide (128-byte) K stages for conv blocks with long reductions on small grids: >= 8 steps of
-// 64 bytes, every stage within one tap (cin_pad % 128 == 0), and few enough tiles that the
-// 2 workgroups per CU the wide ring's LDS allows hold the whole grid (TK_WIDE_MAX_TILES).
-static bool conv_wide(const ConvGeom& g, bool block, int ipt) {
-  if (!block || g.KH * g.KW > 64 || g.cin_pad % 128 != 0 || g.k_pad / kBK < 8 ||
-      !env_int("TK_WIDE", 1) || !env_int("TK_UNITAP", 1) || tune_env("TK_MT2"))
-    return false;
-  const int64_t tiles = conv_ntiles(g, ipt) * ((g.O + 63) / 64);
-  // (256-column tiles: the wide ring holds one workgroup per CU)
-  return tiles <= (conv_bn256_ipt(g, block, false) ? 256 : env_int("TK_WIDE_MAX_TILES", 512));
-}
-
-// 128-row tiles with 128-byte K stages (96 KB ring, one workgroup per CU) where the grid fits one
-// round: the 14x14 3x3 256-channel layers, -5.5 % (profiles/r02z_wide_mt2_ab.txt)
-static bool wide_mt2(const ConvGeom& g, int64_t tiles) {
-  return g.KH * g.KW <= 64 && g.cin_pad % 128 == 0 && g.k_pad / kBK >= 8 && tiles <= 256 && env_int("TK_WIDE_MT2", 1);
-}
-
-static SplitPlan conv_split_plan(const ConvGeom& g, bool mt1, int ipt, int sbk = kBK) {
-  const int64_t tiles = conv_ntiles(g, ipt) * ((g.O + (mt1 ? 63 : 127)) / (mt1 ? 64 : 128));
-  const int nk = (int)(g.k_pad / sbk);
-  SplitPlan sp{1, nk, tiles};
-  // measured: splitting grids of >= 256 tiles (one per CU) loses more to the partial-tile
-  // round trip than it gains in latency hiding
-  if (!mt1 || tiles >= 256) return sp;
-  int want = (int)std::min<int64_t>((768 + tiles - 1) / tiles, nk / 6);
-  if (want <= 1) return sp;
-  sp.kper = (nk + want - 1) / want;
-  sp.splits = (nk + sp.kper - 1) / sp.kper;
-  return sp;
-}
-
-
-static inline int64_t al256(int64_t v) { return (v + 255) / 256 * 256; }
-
-int64_t conv_scratch_bytes(const tk_tensor* data, const tk_tensor* weight, const tk_conv2d_attrs* a, int block) {
-  if (!a) return -1;
-  ConvGeom g;
-  if (conv_geom(data, weight, a, &g) != TK_OK) return -1;
-  if (!use_mfma_conv(g, a->groups)) return 0;
-  int64_t bytes = 0;
-  if (conv_needs_patch(weight, a)) bytes += al256((int64_t)g.N * g.OH * g.OW * 4);
-  const bool mt1 = conv_mt1(g, block);
-  const int ipt = mt1 ? conv_image_tiles(g, block, conv_needs_patch(weight, a)) : 0;
-  const bool wide = mt1 && conv_wide(g, block, ipt);
-  const SplitPlan sp = conv_split_plan(g, mt1, ipt, wide ? 2 * kBK : kBK);
-  int64_t split = sp.splits > 1 ? al256(sp.tiles * sp.splits * (int64_t)(2 * 16 * kGemmThreads) * 4) : 0;
-  // a conv block's split-K image-tile plans (3x3) use the same space for their partial records
-  if (block && !conv_needs_patch(weight, a)) {
-    split = std::max(split, al256(conv_img_split_scratch_bytes(g)));
-    split = std::max(split, al256(conv_dense_scratch_bytes(g)));  // the dense head's K-slice sums
-  }
-  return bytes + split;
-}
-
-static int conv2d_run(const tk_tensor* data, const void* shadow, const tk_tensor* weight, const void* packed,
-                      const int32_t* sums, tk_tensor* out, const tk_conv2d_attrs* a, void* scratch,
-                      const BlockIO* blk, hipStream_t s) {
-  TK_CHECK_ARG(data && weight && out && a, "null argument");
-  TK_CHECK_ARG(is_int8ish(data) && is_int8ish(weight) && is_int(out, 32), "dtypes: int8/uint8 in, int32 out");
-  ConvGeom g;
-  if (conv_geom(data, weight, a, &g) != TK_OK) {
-    set_error("tk_qnn_conv2d: bad shapes");
-    return TK_ERR_SHAPE;
-  }
-  TK_CHECK_ARG(out->ndim == 4 && out->shape[0] == g.N && out->shape[1] == g.O && out->shape[2] == g.OH &&
-                   out->shape[3] == g.OW,
-               "output shape mismatch");
-  TK_CHECK_ARG(a->strides[0] > 0 && a->strides[1] > 0 && a->dilation[0] > 0 && a->dilation[1] > 0, "bad strides");
-  int64_t P = (int64_t)g.N * g.OH * g.OW;
-  TK_CHECK_ARG(P < INT32_MAX && (int64_t)g.N * g.O * g.OH * g.OW < INT32_MAX * 2LL, "tensor too large");
-  GemmArgs ga{};
-  ga.C = (int32_t*)ptr(out);
-  ga.M = g.O;
-  ga.N = (int32_t)P;
-  ga.OH = g.OH;
-  ga.OW = g.OW;
-  ga.ch_is_row = 1;
-  ga.ablate = ablate_flags();
-  ga.nt = nt_stores();
-  ga.xcd_order = xcd_order((int64_t)g.OH * g.OW);
-  int rc = setup_block(ga, blk, out, g.O, 1);
-  if (rc) return rc;
-  if (!use_mfma_conv(g, a->groups)) {
-    TK_CHECK_ARG(!(blk && blk->attrs->has_add), "residual join needs an MFMA conv block");
-    // depthwise 3x3 blocks, every plane size: the tile kernel of tk_dw.hip (TK_DW2=0 in the
-    // ablation build keeps the older band / direct kernels below for A/B)
-    if (blk && env_int("TK_DW2", 1)) {
-      int rc_dw = TK_OK;
-      if (dw_block_try(data, weight, g, a, ga, s, &rc_dw)) return rc_dw;
+int gemm_launch(const GemmVariant& v, dim3 grid, unsigned lds_pad, const GemmArgs& ga, hipStream_t s) {
+  for (const GemmKernel& k : kGemmKernels)
+    if (k.key == v) {
+      hipLaunchKernelGGL(k.fn, grid, dim3(kGemmThreads), lds_pad, s, ga);
+      TK_LAUNCH_CHECK();
+      return TK_OK;
     }
-    // depthwise 3x3 blocks: the LDS-staged band kernel (see dw3x3_kernel)
-    // (large planes only: on 7x7 / 14x14 planes and strided 28x28 ones the generic kernel measured
-    // faster, the band staging does not amortise; MobileNetV2 dw layers 1.2-2x faster otherwise)
-    const int64_t ohw = (int64_t)g.OH * g.OW;
-    if (blk && a->groups == g.C && g.C == g.O && g.C % 16 == 0 && g.KH == 3 && g.KW == 3 && a->dilation[0] == 1 &&
-        a->dilation[1] == 1 && ((a->strides[0] == 1 && ohw >= 784) || ohw >= 3136) && env_int("TK_DW", 1)) {
-      const int sh = a->strides[0], sw = a->strides[1];
-      // output pixels per workgroup and channel: whole planes up to 1024 pixels, else bands of
-      // ~512 (stride 1) / ~256 (stride 2) pixels (measured on MobileNetV2's 112x112 and 56x56 layers)
-      const int budget = env_int("TK_DW_BUDGET", sh == 1 ? 512 : 256);
-      const int BH = g.OH * g.OW <= 1024 ? g.OH : std::max(1, budget / g.OW);
-      const int bands = (g.OH + BH - 1) / BH;
-      const int Wp = g.W + 8;  // input row + 4-byte halos (see dw3x3_kernel)
-      const int rows_max = (BH - 1) * sh + 3;
-      const size_t lds = (size_t)((16 * rows_max * Wp + 15) & ~15) + 16 * 9 * 4 + (size_t)BH * g.OW * 16;
-      const bool fits = g.W % 4 == 0 && g.W <= 248 && a->padding[1] <= 4 && (g.OW - 1) * sw + 2 - a->padding[1] < g.W + 4;
-      if (lds <= 64 * 1024 && fits) {
-        const unsigned grid = (unsigned)((int64_t)g.N * (g.C / 16) * bands);
-        const bool v4 = g.OW % 4 == 0;
-#define TK_DW(TX, TW)                                                                                              \
-  if (v4)                                                                                                          \
-    hipLaunchKernelGGL((dw3x3_kernel<TX, TW, 4>), dim3(grid), dim3(256), lds, s, (const TX*)ptr(data),            \
-                       (const TW*)ptr(weight), g.C, g.H, g.W, g.OH, g.OW, sh, sw, a->padding[0], a->padding[1],     \
-                       a->input_zero_point, a->kernel_zero_point, a->kernel_zero_points, BH, bands, Wp, ga);      \
-  else                                                                                                             \
-    hipLaunchKernelGGL((dw3x3_kernel<TX, TW, 1>), dim3(grid), dim3(256), lds, s, (const TX*)ptr(data),            \
-                       (const TW*)ptr(weight), g.C, g.H, g.W, g.OH, g.OW, sh, sw, a->padding[0], a->padding[1],     \
-                       a->input_zero_point, a->kernel_zero_point, a->kernel_zero_points, BH, bands, Wp, ga)
-        const bool du = is_uint(data, 8), wu = is_uint(weight, 8);
-        if (du && wu) { TK_DW(uint8_t, uint8_t); }
-        else if (du) { TK_DW(uint8_t, int8_t); }
-        else if (wu) { TK_DW(int8_t, uint8_t); }
-        else { TK_DW(int8_t, int8_t); }
-#undef TK_DW
-        TK_LAUNCH_CHECK();
-        return TK_OK;
-      }
-    }
-    // grouped / depthwise / tiny channel counts: direct VALU kernel on NCHW
-    int64_t total = (int64_t)g.N * g.O * g.OH * g.OW;
-    int grid = (int)std::max<int64_t>(1, std::min<int64_t>((total + 255) / 256, 8192));
-#define TK_DIRECT(TX, TW, BLK)                                                                                   \
-  hipLaunchKernelGGL((direct_conv_kernel<TX, TW, BLK>), dim3(grid), dim3(256), 0, s, (const TX*)ptr(data),        \
-                     (const TW*)ptr(weight), g.N, g.C, g.H, g.W, g.O, g.OH, g.OW, g.KH, g.KW, a->strides[0],          \
-                     a->strides[1], a->padding[0], a->padding[1], a->dilation[0], a->dilation[1], a->groups,         \
-                     a->input_zero_point, a->kernel_zero_point, a->kernel_zero_points, ga)
-#define TK_DIRECT_B(TX, TW) \
-  if (blk) TK_DIRECT(TX, TW, true); else TK_DIRECT(TX, TW, false)
-    bool du = is_uint(data, 8), wu = is_uint(weight, 8);
-    if (du && wu) { TK_DIRECT_B(uint8_t, uint8_t); }
-    else if (du) { TK_DIRECT_B(uint8_t, int8_t); }
-    else if (wu) { TK_DIRECT_B(int8_t, uint8_t); }
-    else { TK_DIRECT_B(int8_t, int8_t); }
-#undef TK_DIRECT_B
-#undef TK_DIRECT
-    TK_LAUNCH_CHECK();
-    return TK_OK;
-  }
-  TK_CHECK_ARG(shadow && packed && sums, "MFMA conv needs shadow, packed weight and weight sums");
-  int du = is_uint(data, 8), wu = is_uint(weight, 8);
-  TK_CHECK_ARG(!(wu && a->kernel_zero_points), "per-channel zero points with uint8 weights are not supported");
-  int32_t za = a->input_zero_point - (du ? 128 : 0);
-  int32_t zw = a->kernel_zero_point - (wu ? 128 : 0);
-  ga.A = (const int8_t*)packed;
-  ga.B = (const int8_t*)shadow;
-  ga.lda = g.k_pad;
-  ga.ldb = g.cin_pad;
-  ga.k_pad = g.k_pad;
-  ga.k_eff = g.k_eff;
-  // operand A = weights (zero point zw), operand B = activations (zero point za)
-  ga.zA = zw;
-  ga.zB = za;
-  ga.RA = sums;
-  ga.H = g.H; ga.W = g.W; ga.cin_pad = g.cin_pad; ga.KH = g.KH; ga.KW = g.KW;
-  ga.in_pix = (int64_t)g.N * g.H * g.W;
-  ga.sh = a->strides[0]; ga.sw = a->strides[1]; ga.pt = a->padding[0]; ga.pl = a->padding[1];
-  ga.dh = a->dilation[0]; ga.dw = a->dilation[1];
-  ga.taps = g.KH * g.KW;
-  ga.cgroups = g.cin_pad / 16;
-  ga.unitap = ga.taps <= 64 && (g.cin_pad % kBK == 0 || ga.taps == 1) && env_int("TK_UNITAP", 1);
-  {
-    // (p * ceil(2^40 / d)) >> 40 == p / d while p * d < 2^40
-    const uint64_t hw = (uint64_t)g.OH * g.OW;
-    auto magic = [](uint64_t d, uint64_t pmax) -> uint64_t {
-      return pmax * d < (1ull << 40) ? ((1ull << 40) + d - 1) / d : 0;
-    };
-    ga.mg_hw = magic(hw, (uint64_t)P);
-    ga.mg_ow = magic((uint64_t)g.OW, hw);
-  }
-  ga.fill = rep4(za);
-  {
-    const uint64_t elems = (uint64_t)P * g.O;
-    ga.out_elems = (uint32_t)std::min<uint64_t>(elems, 0xFFFFFFFFull);
-    const int mode = blk ? blk->attrs->requantize.mode : -1;
-    // record stores are nontemporal (1) only where a plane's int32 rows are whole 128-byte
-    // lines (or planes are tiny): measured on ResNet-50, partial-line NT stores (28x28, 14x14
-    // planes) run up to 1.9x slower than plain ones, which the L2 merges before write-back
-    const int hwp = g.OH * g.OW;
-    const int epi = hwp % 32 == 0 || hwp <= 64 ? 1 : 2;
-    ga.fast_epi = blk && elems * 4 < 0xFFFFFFC0ull && hwp % 4 == 0 && block_rq_fast_mode(mode) ? env_int("TK_FASTEPI", epi) : 0;
-  }
-  ga.out_nchw = 1;
-  {
-    const int hwv = g.OH * g.OW;  // store vectors must not straddle an image plane
-    ga.vecw = hwv % 4 == 0 ? 4 : 1;
-  }
-  char* sc = (char*)scratch;
-  if (conv_needs_patch(weight, a)) {
-    TK_CHECK_ARG(sc, "non-zero kernel zero point needs scratch (tk_conv2d_scratch_bytes)");
-    int32_t* ps = (int32_t*)sc;
-    sc += al256(P * 4);
-    int grid = (int)std::max<int64_t>(1, std::min<int64_t>((P + 255) / 256, 4096));
-    hipLaunchKernelGGL(patch_sum_kernel, dim3(grid), dim3(256), 0, s, (const int8_t*)shadow, ps, ga, g.C);
-    TK_LAUNCH_CHECK();
-    ga.RB = ps;
-    ga.zA_vec = a->kernel_zero_points;
-  }
-  if (blk && blk->attrs->algo == kAlgoDense) {
-    if (!conv_dense_applies(g, ga)) {
-      set_error("tk_qnn_conv2d_block: algo 5 (dense tiles) does not apply to this block; see tk_conv2d_block_algos");
-      return TK_ERR_INVALID_ARG;
-    }
-    return conv_dense_run(g, ga, sc, s);
-  }
-  if (blk) {
-    // whole-image tiles with the patch staged per channel stage (tk_conv_img.hip) where they apply
-    const int8_t* chunked = conv_img_chunked_bytes(g.rows_pad, g.cin_pad, g.KH * g.KW)
-                                ? (const int8_t*)packed + (int64_t)g.rows_pad * g.k_pad
-                                : nullptr;
-    int irc = TK_OK;
-    if (conv_img_try(g, a, ga, chunked, sc, blk->attrs->algo, s, &irc)) return irc;
-    const int algo = blk->attrs->algo;
-    if (algo == kAlgoPf2 || algo == kAlgoPf3) {
-      if (!conv_pf_applies(g, ga)) {
-        set_error("tk_qnn_conv2d_block: algo " + std::to_string(algo) +
-                  " (persistent im2col) does not apply to this conv; see tk_conv2d_block_algos");
-        return TK_ERR_INVALID_ARG;
-      }
-      return conv_pf_run(g, ga, algo == kAlgoPf2 ? 2 : 3, s);
-    }
-  }
-  const bool mt1 = conv_mt1(g, blk != nullptr);
-  const int ipt = mt1 ? conv_image_tiles(g, blk != nullptr, conv_needs_patch(weight, a)) : 0;
-  ga.ipt = ipt;
-  const bool bn_rows = mt1 && !ipt && conv_bn256_rows(g, blk != nullptr, conv_needs_patch(weight, a));
-  ga.tcols = ipt ? ipt * g.OH * g.OW : bn_rows ? 256 : 128;
-  const bool bn256 = bn_rows || (mt1 && conv_bn256_ipt(g, blk != nullptr, conv_needs_patch(weight, a)) != 0);
-  ga.ntiles = bn_rows ? (int32_t)((P + 255) / 256) : (int32_t)conv_ntiles(g, ipt);
-  ga.ntiles8 = (ga.ntiles + 7) / 8 * 8;
-  ga.mtiles = (g.O + (mt1 ? 63 : 127)) / (mt1 ? 64 : 128);
-  dim3 grid((unsigned)((int64_t)ga.mtiles * ga.ntiles8));
-  const bool wide = mt1 && conv_wide(g, blk != nullptr, ipt);
-  const SplitPlan sp = conv_split_plan(g, mt1, ipt, wide ? 2 * kBK : kBK);
-  const int ring = ring_depth();
-  if (sp.splits > 1) {
-    TK_CHECK_ARG(sc, "split-K conv needs scratch (tk_conv2d_scratch_bytes)");
-    ga.ws = (int32_t*)sc;
-    ga.splits = sp.splits;
-    ga.kper = sp.kper;
-    dim3 pgrid(grid.x, 1, (unsigned)sp.splits);
-    if (wide) hipLaunchKernelGGL((gemm_i8_kernel<1, true, false, 1, 3, true>), pgrid, dim3(kGemmThreads), 0, s, ga);
-    else switch (ring) {
-      case 4: hipLaunchKernelGGL((gemm_i8_kernel<1, true, false, 1, 4>), pgrid, dim3(kGemmThreads), 0, s, ga); break;
-      case 5: hipLaunchKernelGGL((gemm_i8_kernel<1, true, false, 1, 5>), pgrid, dim3(kGemmThreads), 0, s, ga); break;
-      default: hipLaunchKernelGGL((gemm_i8_kernel<1, true, false, 1>), pgrid, dim3(kGemmThreads), 0, s, ga);
-    }
-    TK_LAUNCH_CHECK();
-    if (blk) hipLaunchKernelGGL((gemm_i8_kernel<1, true, true, 2>), grid, dim3(kGemmThreads), 0, s, ga);
-    else hipLaunchKernelGGL((gemm_i8_kernel<1, true, false, 2>), grid, dim3(kGemmThreads), 0, s, ga);
-  } else if (bn256) {
-    if (wide) hipLaunchKernelGGL((gemm_i8_kernel<1, true, true, 0, 3, true, 256>), grid, dim3(kGemmThreads), 0, s, ga);
-    else hipLaunchKernelGGL((gemm_i8_kernel<1, true, true, 0, 3, false, 256>), grid, dim3(kGemmThreads), 0, s, ga);
-  } else if (mt1) {
-    if (blk) {
-      const unsigned pad = (unsigned)env_int("TK_LDS_PAD", 0);  // profiling: extra LDS per workgroup
-      if (wide) switch (ring) {
-        case 4: hipLaunchKernelGGL((gemm_i8_kernel<1, true, true, 0, 4, true>), grid, dim3(kGemmThreads), pad, s, ga); break;
-        case 5: hipLaunchKernelGGL((gemm_i8_kernel<1, true, true, 0, 5, true>), grid, dim3(kGemmThreads), pad, s, ga); break;
-        default: hipLaunchKernelGGL((gemm_i8_kernel<1, true, true, 0, 3, true>), grid, dim3(kGemmThreads), pad, s, ga);
-      }
-      else switch (ring) {
-        case 4: hipLaunchKernelGGL((gemm_i8_kernel<1, true, true, 0, 4>), grid, dim3(kGemmThreads), pad, s, ga); break;
-        case 5: hipLaunchKernelGGL((gemm_i8_kernel<1, true, true, 0, 5>), grid, dim3(kGemmThreads), pad, s, ga); break;
-        default: hipLaunchKernelGGL((gemm_i8_kernel<1, true, true>), grid, dim3(kGemmThreads), pad, s, ga);
-      }
-    } else {
-      hipLaunchKernelGGL((gemm_i8_kernel<1, true, false>), grid, dim3(kGemmThreads), 0, s, ga);
-    }
-  } else {
-    if (blk && wide_mt2(g, ga.mtiles * (int64_t)ga.ntiles))
-      hipLaunchKernelGGL((gemm_i8_kernel<2, true, true, 0, 3, true>), grid, dim3(kGemmThreads), 0, s, ga);
-    else if (blk) hipLaunchKernelGGL((gemm_i8_kernel<2, true, true>), grid, dim3(kGemmThreads), 0, s, ga);
-    else hipLaunchKernelGGL((gemm_i8_kernel<2, true, false>), grid, dim3(kGemmThreads), 0, s, ga);
-  }
-  TK_LAUNCH_CHECK();
-  return TK_OK;
-}
-
-int conv2d_prepared_impl(const tk_tensor* data, const void* shadow, const tk_tensor* weight, const void* packed,
-                         const int32_t* sums, tk_tensor* out, const tk_conv2d_attrs* a, void* workspace_patch,
-                         hipStream_t s) {
-  return conv2d_run(data, shadow, weight, packed, sums, out, a, workspace_patch, nullptr, s);
-}
-
-int conv2d_block_impl(const tk_tensor* data, const void* shadow, const tk_tensor* weight, const void* packed,
-                      const int32_t* sums, const tk_tensor* bias, tk_tensor* const* outs, int n_outs,
-                      const tk_block_attrs* attrs, void* patch, void* shadow_out, hipStream_t s) {
-  TK_CHECK_ARG(outs && n_outs >= 3 && outs[0], "block needs outputs");
-  BlockIO b{bias, outs, n_outs, attrs, shadow_out};
-  return conv2d_run(data, shadow, weight, packed, sums, outs[0], attrs ? &attrs->conv : nullptr, patch, &b, s);
-}
-
-// what the image-tile planner reads of a block's launch arguments (see conv2d_run)
-static GemmArgs planner_args(const ConvGeom& g, const tk_tensor* weight, const tk_block_attrs* attrs) {
-  static int32_t marker;
-  GemmArgs ga{};
-  ga.bias_out = &marker;
-  ga.has_add = attrs->has_add;
-  ga.in_pix = (int64_t)g.N * g.H * g.W;
-  ga.zA = attrs->conv.kernel_zero_point - (is_uint(weight, 8) ? 128 : 0);
-  ga.zA_vec = attrs->conv.kernel_zero_points;
-  ga.RB = conv_needs_patch(weight, &attrs->conv) ? &marker : nullptr;
-  return ga;
-}
-
-int conv_img_describe(const ConvGeom& g, const tk_conv2d_attrs* a, const GemmArgs& ga, bool have_chunked, int algo,
-                      char* buf, int len);
-
-int conv2d_block_algo_info_impl(const tk_tensor* data, const tk_tensor* weight, const tk_block_attrs* attrs, int algo,
-                                char* buf, int len) {
-  TK_CHECK_ARG(data && weight && attrs && buf && len > 0, "null argument");
-  ConvGeom g;
-  if (conv_geom(data, weight, &attrs->conv, &g) != TK_OK) {
-    set_error("tk_conv2d_block_algo_info: bad shapes");
-    return TK_ERR_SHAPE;
-  }
-  const GemmArgs ga = planner_args(g, weight, attrs);
-  const char* fixed = algo == kAlgoIm2col ? "im2col tiles (64 or 128 rows x 128 or 256 columns, the library's own shape)"
-                      : algo == kAlgoPf2  ? "persistent im2col tiles, 2 workgroups per CU"
-                      : algo == kAlgoPf3  ? "persistent im2col tiles, 1 workgroup per CU (3-slot ring)"
-                      : algo == kAlgoDense ? "dense tiles: 32 units x 64 samples, K split over 8 waves"
-                                           : nullptr;
-  if (fixed) {
-    std::snprintf(buf, (size_t)len, "%s", fixed);
-    return TK_OK;
-  }
-  const int rc = conv_img_describe(g, &attrs->conv, ga,
-                                   g.KH * g.KW == 1 || conv_img_chunked_bytes(g.rows_pad, g.cin_pad, g.KH * g.KW), algo,
-                                   buf, len);
-  if (rc) set_error("tk_conv2d_block_algo_info: algo " + std::to_string(algo) + " is not listed for this block");
-  return rc;
-}
-
-int conv2d_block_algos_impl(const tk_tensor* data, const tk_tensor* weight, const tk_block_attrs* attrs,
-                            int32_t* algos, int max_algos) {
-  TK_CHECK_ARG(data && weight && attrs && (algos || max_algos <= 0), "null argument");
-  ConvGeom g;
-  if (conv_geom(data, weight, &attrs->conv, &g) != TK_OK) {
-    set_error("tk_conv2d_block_algos: bad shapes");
-    return TK_ERR_SHAPE;
-  }
-  if (!use_mfma_conv(g, attrs->conv.groups) || !is_int8ish(data) || !is_int8ish(weight)) return 0;
-  const GemmArgs ga = planner_args(g, weight, attrs);
-  int n = 0;
-  // dense blocks (1x1 over [B, K, 1, 1]) with a zero weight zero point: the dense tile kernel first
-  if (conv_dense_applies(g, ga)) {
-    if (n < max_algos) algos[n] = kAlgoDense;
-    ++n;
-  }
-  if (n < max_algos) algos[n] = kAlgoIm2col;
-  ++n;
-  n += conv_img_algos(g, &attrs->conv, ga, g.KH * g.KW == 1 || conv_img_chunked_bytes(g.rows_pad, g.cin_pad, g.KH * g.KW),
-                      algos && max_algos > n ? algos + n : nullptr, max_algos - n);
-  // the persistent im2col kernel, last: it measured slower than the im2col kernel on every
-  // ResNet-50 layer (profiles/r03w_find_step_pf.json), so the find step's first candidates stay
-  // the image-tile plans; listed where conv2d_run's arguments will meet conv_pf_applies
-  {
-    const int64_t P = (int64_t)g.N * g.OH * g.OW, hw = (int64_t)g.OH * g.OW;
-    const int mode = attrs->requantize.mode;
-    const int taps = g.KH * g.KW;
-    GemmArgs pa = ga;
-    // the same gates (incl. the TK_FASTEPI / TK_UNITAP overrides) as conv2d_run, so that every
-    // algo listed here runs there
-    const int epi = hw % 32 == 0 || hw <= 64 ? 1 : 2;
-    pa.fast_epi = P * g.O * 4 < 0xFFFFFFC0ll && hw % 4 == 0 && block_rq_fast_mode(mode) ? env_int("TK_FASTEPI", epi) : 0;
-    pa.unitap = taps <= 64 && (g.cin_pad % kBK == 0 || taps == 1) && env_int("TK_UNITAP", 1);
-    pa.ch_is_row = 1;
-    pa.out_nchw = 1;
-    pa.shadow_out = nullptr;  // (bounded like the records)
-    if (conv_pf_applies(g, pa) && (int64_t)(g.O + 15) / 16 * 16 * P < 0xFFFFFF00ll) {
-      for (int al : {kAlgoPf2, kAlgoPf3}) {
-        if (n < max_algos) algos[n] = al;
-        ++n;
-      }
-    }
-  }
-  return n;
-}
-
-int64_t conv2d_workspace_bytes(const tk_tensor* data, const tk_tensor* weight, const tk_conv2d_attrs* a) {
-  if (!a) return -1;
-  ConvGeom g;
-  if (conv_geom(data, weight, a, &g) != TK_OK) return -1;
-  if (!use_mfma_conv(g, a->groups)) return 0;
-  int64_t packed = conv_packed_weight_bytes(weight, 1);
-  int64_t sums = (int64_t)g.rows_pad * 4;
-  int64_t shadow = conv_shadow_bytes(data);
-  auto al = [](int64_t v) { return (v + 255) / 256 * 256; };
-  return al(packed) + al(sums) + al(shadow) + conv_scratch_bytes(data, weight, a, 0);
-}
-
-int conv2d_impl(const tk_tensor* data, const tk_tensor* weight, tk_tensor* out, const tk_conv2d_attrs* a,
-                void* workspace, hipStream_t s) {
-  TK_CHECK_ARG(data && weight && out && a, "null argument");
-  ConvGeom g;
-  if (conv_geom(data, weight, a, &g) != TK_OK) {
-    set_error("tk_qnn_conv2d: bad shapes");
-    return TK_ERR_SHAPE;
-  }
-  if (!use_mfma_conv(g, a->groups))
-    return conv2d_run(data, nullptr, weight, nullptr, nullptr, out, a, nullptr, nullptr, s);
-  TK_CHECK_ARG(workspace, "workspace required (tk_qnn_conv2d_workspace_bytes)");
-  auto al = [](int64_t v) { return (v + 255) / 256 * 256; };
-  char* ws = (char*)workspace;
-  void* packed = ws;
-  ws += al(conv_packed_weight_bytes(weight, 1));
-  int32_t* sums = (int32_t*)ws;
-  ws += al((int64_t)g.rows_pad * 4);
-  void* shadow = ws;
-  ws += al(conv_shadow_bytes(data));
-  void* scratch = ws;
-  int rc = conv_pack_weight(weight, 1, packed, sums, s);
-  if (rc) return rc;
-  rc = make_shadow_impl(data, shadow, s);
-  if (rc) return rc;
-  return conv2d_run(data, shadow, weight, packed, sums, out, a, scratch, nullptr, s);
+  set_error("gemm_i8_kernel: no instantiation with MT " + std::to_string(v.mt) + ", im2col " + std::to_string(v.im2col) +
+            ", block " + std::to_string(v.block) + ", mode " + std::to_string(v.mode) + ", ring " +
+            std::to_string(v.ring) + ", wide " + std::to_string(v.wide) + ", BN " + std::to_string(v.bn));
+  return TK_ERR_INVALID_ARG;
 }
 
 // ---------------------------------------------------------------- dense
-// Split-K of a dense GEMM (MT = 2 tiles, 128 x 128): classifier heads have a handful of
-// tiles and a long K (ResNet-50 fc: 8 tiles, 32 k-steps), so split until ~512 workgroups
-// run, keeping >= 2 k-steps per split.
-static SplitPlan dense_split_plan(int64_t M, int64_t Nn, int64_t K) {
-  const int64_t tiles = ((M + 127) / 128) * ((Nn + 127) / 128);
-  const int nk = (int)((K + kBK - 1) / kBK);
-  SplitPlan sp{1, nk, tiles};
-  if (tiles >= 256) return sp;
-  // the reduce pass reads splits sequentially: a few splits already fill the chip
-  int want = (int)std::min<int64_t>(std::min<int64_t>((512 + tiles - 1) / tiles, nk / 2), 4);
-  if (want <= 1) return sp;
-  sp.kper = (nk + want - 1) / want;
-  sp.splits = (nk + sp.kper - 1) / sp.kper;
-  return sp;
-}
 
 int64_t dense_workspace_bytes(const tk_tensor* data, const tk_tensor* weight) {
   if (!data || !weight || data->ndim != 2 || weight->ndim != 2) return -1;
-  int64_t M = data->shape[0], K = data->shape[1], Nn = weight->shape[0];
-  int64_t k_pad = (K + kBK - 1) / kBK * kBK;
-  int64_t mrows = (M + 127) / 128 * 128, nrows = (Nn + 127) / 128 * 128;
-  auto al = [](int64_t v) { return (v + 255) / 256 * 256; };
-  const SplitPlan sp = dense_split_plan(M, Nn, K);
-  const int64_t partial = sp.splits > 1 ? sp.tiles * sp.splits * (int64_t)(2 * 2 * 16 * kGemmThreads) * 4 : 0;
-  return al(mrows * k_pad) + al(nrows * k_pad) + al(mrows * 4) + al(nrows * 4) + al(partial);
+  return dense_plan(data->shape[0], weight->shape[0], data->shape[1], false).bytes;
 }
 
 static int dense_run(const tk_tensor* data, const tk_tensor* weight, tk_tensor* out, const tk_dense_attrs* a,
@@ -2105,25 +1094,18 @@ static int dense_run(const tk_tensor* data, const tk_tensor* weight, tk_tensor* 
   TK_CHECK_ARG(is_int8ish(data) && is_int8ish(weight) && is_int(out, 32), "dtypes: int8/uint8 in, int32 out");
   int M = (int)data->shape[0], K = (int)data->shape[1], Nn = (int)weight->shape[0];
   TK_CHECK_ARG(weight->shape[1] == K && out->shape[0] == M && out->shape[1] == Nn, "shape mismatch");
-  int k_pad = (K + kBK - 1) / kBK * kBK;
-  int mrows = (M + 127) / 128 * 128, nrows = (Nn + 127) / 128 * 128;
-  auto al = [](int64_t v) { return (v + 255) / 256 * 256; };
+  const DensePlan d = dense_plan(M, Nn, K, blk != nullptr);
   char* ws = (char*)workspace;
-  int8_t* dpad = (int8_t*)ws;
-  ws += al((int64_t)mrows * k_pad);
-  int8_t* wpad = (int8_t*)ws;
-  ws += al((int64_t)nrows * k_pad);
-  int32_t* dsum = (int32_t*)ws;
-  ws += al((int64_t)mrows * 4);
-  int32_t* wsum = (int32_t*)ws;
-  ws += al((int64_t)nrows * 4);
-  int32_t* partial = (int32_t*)ws;
+  int8_t* dpad = (int8_t*)(ws + d.pad_a);
+  int8_t* wpad = (int8_t*)(ws + d.pad_b);
+  int32_t* dsum = (int32_t*)(ws + d.sum_a);
+  int32_t* wsum = (int32_t*)(ws + d.sum_b);
   int du = is_uint(data, 8), wu = is_uint(weight, 8);
   TK_CHECK_ARG(!(wu && a->kernel_zero_points), "per-unit zero points with uint8 weights are not supported");
-  hipLaunchKernelGGL(pad_rows_kernel, dim3(mrows), dim3(256), 0, s, (const uint8_t*)ptr(data), dpad, dsum, M, K, k_pad, du);
-  hipLaunchKernelGGL(pad_rows_kernel, dim3(nrows), dim3(256), 0, s, (const uint8_t*)ptr(weight), wpad, wsum, Nn, K, k_pad,
-                     wu);
-  TK_LAUNCH_CHECK();
+  int rc = dense_pad_rows(data, dpad, dsum, d.mrows, d.k_pad, s);
+  if (rc) return rc;
+  rc = dense_pad_rows(weight, wpad, wsum, d.nrows, d.k_pad, s);
+  if (rc) return rc;
   int32_t za = a->input_zero_point - (du ? 128 : 0);
   int32_t zw = a->kernel_zero_point - (wu ? 128 : 0);
   GemmArgs ga{};
@@ -2132,9 +1114,9 @@ static int dense_run(const tk_tensor* data, const tk_tensor* weight, tk_tensor* 
   ga.C = (int32_t*)ptr(out);
   ga.M = M;
   ga.N = Nn;
-  ga.lda = k_pad;
-  ga.ldb = k_pad;
-  ga.k_pad = k_pad;
+  ga.lda = d.k_pad;
+  ga.ldb = d.k_pad;
+  ga.k_pad = d.k_pad;
   ga.k_eff = K;
   ga.zA = za;              // operand A = data
   ga.zB = zw;              // operand B = weights
@@ -2146,30 +1128,22 @@ static int dense_run(const tk_tensor* data, const tk_tensor* weight, tk_tensor* 
   ga.vecw = Nn % 4 == 0 ? 4 : 1;
   ga.ch_is_row = 0;
   TK_CHECK_ARG(!(blk && blk->attrs->has_add), "residual join is supported on conv blocks only");
-  int rc = setup_block(ga, blk, out, Nn, 1);
+  rc = setup_block(ga, blk, out, Nn, 1);
   if (rc) return rc;
   ga.shadow_out = nullptr;
   ga.tcols = 128;
-  ga.ntiles = (int32_t)((Nn + 127) / 128);
-  ga.ntiles8 = (ga.ntiles + 7) / 8 * 8;
-  ga.mtiles = (M + 127) / 128;
-  dim3 grid((unsigned)((int64_t)ga.mtiles * ga.ntiles8));
-  const SplitPlan sp = dense_split_plan(M, Nn, K);
-  if (sp.splits > 1) {
-    ga.ws = partial;
-    ga.splits = sp.splits;
-    ga.kper = sp.kper;
-    hipLaunchKernelGGL((gemm_i8_kernel<2, false, false, 1>), dim3(grid.x, 1, sp.splits), dim3(kGemmThreads), 0, s, ga);
-    TK_LAUNCH_CHECK();
-    if (blk) hipLaunchKernelGGL((gemm_i8_kernel<2, false, true, 2>), grid, dim3(kGemmThreads), 0, s, ga);
-    else hipLaunchKernelGGL((gemm_i8_kernel<2, false, false, 2>), grid, dim3(kGemmThreads), 0, s, ga);
-  } else if (blk) {
-    hipLaunchKernelGGL((gemm_i8_kernel<2, false, true>), grid, dim3(kGemmThreads), 0, s, ga);
-  } else {
-    hipLaunchKernelGGL((gemm_i8_kernel<2, false, false>), grid, dim3(kGemmThreads), 0, s, ga);
+  ga.ntiles = d.ntiles;
+  ga.ntiles8 = d.ntiles8;
+  ga.mtiles = d.mtiles;
+  const dim3 grid((unsigned)((int64_t)d.mtiles * d.ntiles8));
+  if (d.splits > 1) {
+    ga.ws = (int32_t*)(ws + d.partials);
+    ga.splits = d.splits;
+    ga.kper = d.kper;
+    rc = gemm_launch(d.main, dim3(grid.x, 1, (unsigned)d.splits), 0, ga, s);
+    return rc ? rc : gemm_launch(d.reduce, grid, 0, ga, s);
   }
-  TK_LAUNCH_CHECK();
-  return TK_OK;
+  return gemm_launch(d.main, grid, 0, ga, s);
 }
 
 int dense_impl(const tk_tensor* data, const tk_tensor* weight, tk_tensor* out, const tk_dense_attrs* a,

@@ -39,7 +39,7 @@ int cast_f32_impl(const tk_tensor* x, tk_tensor* y, hipStream_t s);
 int bias_add_f32_impl(const tk_tensor* x, const tk_tensor* b, tk_tensor* y, int axis, hipStream_t s);
 int global_avg_pool_f32_impl(const tk_tensor* x, tk_tensor* y, hipStream_t s);
 int max_pool_f32_impl(const tk_tensor* x, tk_tensor* y, const tk_pool2d_attrs* a, hipStream_t s);
-// tk_gemm.hip
+// tk_conv_prep.hip (packed weight, shadow), tk_conv.cc (conv), tk_gemm.hip (dense)
 int64_t conv_packed_weight_bytes(const tk_tensor* weight, int groups);
 int conv_pack_weight(const tk_tensor* weight, int groups, void* packed, int32_t* sums, hipStream_t s);
 int64_t conv_shadow_bytes(const tk_tensor* data);

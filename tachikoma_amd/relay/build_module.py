@@ -698,7 +698,7 @@ def exec_groups(plan: Plan, fuse: bool = True) -> List[ExecGroup]:
         if len(cs) != 1 or cs[0].op != "qnn.add" or cs[0].name in taken:
             return None
         add = cs[0]
-        # only the MFMA conv kernels have the fused join (csrc/tk_gemm.hip, use_mfma_conv: one group,
+        # only the MFMA conv kernels have the fused join (csrc/tk_conv_plan.cc, use_mfma_conv: one group,
         # at least 16 output and 3 input channels); a smaller conv keeps its block and the add its own
         w_shape = plan.tensor(chain[0].inputs[1]).shape
         if chain[0].attrs.get("groups", 1) != 1 or w_shape[0] < 16 or w_shape[1] < 3:

@@ -19,7 +19,7 @@ Three lists:
           them, the im2col families run.
   SINGLE  depthwise, grouped and tiny-Cin blocks: one kernel, tk_conv2d_block_algos lists nothing.
           Which kernel, and which of its branches, is in each case's comment (read from
-          dw_block_try in csrc/tk_dw.hip and conv2d_run in csrc/tk_gemm.hip; the kernel names are those
+          dw_block_try in csrc/tk_dw.hip and conv_direct_run in csrc/tk_conv_direct.hip; the kernel names are those
           of profiles/rect_dw_kernel_trace.txt).
 
 What the reference alone gives (test_rect_cases.py asserts the bounds in brackets per geometry; the
